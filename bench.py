@@ -51,10 +51,17 @@ def algorithmic_bytes(m, n, lps, pivots, dives=0):
     return (lps - dives) * load + lps * store + pivots * per_pivot
 
 
+def positive_int(text):
+    v = int(text)
+    if v < 1:   # (the engine reads max_steps <= 0 as "no limit")
+        raise argparse.ArgumentTypeError(f'{text}: at least 1 timed step')
+    return v
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=200)
+    ap.add_argument('--steps', type=positive_int, default=200, help='timed steps (exactly this many)')
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=8192, help='frontier nodes per step per GPU')
     ap.add_argument('--vars', type=int, default=256)
@@ -74,7 +81,34 @@ def parse_args():
                     help='1: after sharding every open node gets an anchor of its own (mipx_tree_reanchor)')
     ap.add_argument('--no-anchor', action='store_true',
                     help='refactor every node from the slack basis instead of the root tableau')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what they computed as DIR/<name>.npy (rank 0)')
     return ap.parse_args()
+
+
+DUMP_BYTES = 48 << 20   # the open-node sample's share; the whole dump stays under 64 MB
+STAT_KEYS = ('evaluated_nodes', 'lp_solved', 'probes_solved', 'pivots', 'open_nodes', 'created_nodes', 'steps',
+             'dual_bound', 'status', 'has_solution', 'dives', 'pool_exhausted')
+
+
+def dump_outputs(out_dir, tree, st):
+    """What a caller of the timed path holds after its last step: the engine's stats (timings left out),
+    the incumbent, the pseudo-cost table and the head of the open-node queue (l, u, basis status, dual
+    bound of the nodes the next step would pop: a deterministic prefix, capped at DUMP_BYTES).
+    incumbent = [primal bound, x]; all zeros while stats' has_solution is 0 (the primal bound is then
+    +inf and there is no x), so that every array is finite."""
+    os.makedirs(out_dir, exist_ok=True)
+    n, nv = tree.problem.n, tree.problem.n + tree.problem.m
+    arrays = {'stats': np.array([st[k] for k in STAT_KEYS], np.float64),
+              'incumbent': np.concatenate([[st['primal_bound']], tree.solution()]) if st['has_solution']
+              else np.zeros(1 + n)}
+    cl, cr, tl, tr = tree.pseudo_cost_arrays()
+    arrays['pseudo_costs'] = np.stack([cl, cr, tl.astype(np.float64), tr.astype(np.float64)])
+    L, U, V, D = tree.peek_open(max(1, DUMP_BYTES // (2 * 8 * n + 4 * nv + 8)))
+    arrays.update(open_l=L, open_u=U, open_vstat=V.astype(np.float32), open_dual_bound=D)
+    for name, a in arrays.items():
+        assert np.all(np.isfinite(a)), f'--dump-outputs: {name} is not finite'
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def spawn_ranks(args):
@@ -603,6 +637,8 @@ def main():
                      d['steps']], dtype=np.float64)
     allr = comm.allgather(mine) if comm is not None else mine[None]
     gstats = tree.global_stats()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, tree, st)
     if comm is not None:
         tree.set_comm(None)
 
