@@ -225,6 +225,34 @@ int mipx_safe_cut_batch(mipx_ctx *ctx, int n, int batch, const double *pi, const
 int mipx_get_fraction_batch(mipx_ctx *ctx, int count, const double *x, const double *max_term,
                             const int32_t *estimate, double *num, double *den);
 
+/*
+ * K4 on its own: the integrality test and branching choice of BaseNode._bound_lp (base_node.py:281-283)
+ * and BaseNode._most_fractional_index (:544-562) / PseudoCostBranchNode._best_pseudo_costs_index
+ * (pseudo_cost.py:118-133) for `batch` solved nodes -- the device code the frontier engine scores with.
+ *   n, batch      columns per node, nodes
+ *   int_idx       n_int integer column indices (each in [0, n)), in the order ties are broken
+ *   x             batch x n   the nodes' LP solutions
+ *   status        batch       Clp status codes; nodes other than 0 / 2 are not lp_feasible
+ *   rule          0 most fractional, 1 pseudo cost
+ *   cost_l/_r, has_entry   n each: the pseudo-cost table by column (rule 1 only, else may be NULL)
+ *   branch_idx    batch  column to branch on, -1 if none (integral, infeasible, or rule 1 with every
+ *                        fractional column still unprobed)
+ *   mip_feasible  batch  max |round-half-even(x_i) - x_i| <= variable_epsilon (0 if not lp_feasible)
+ *   n_unprobed    batch  fractional columns without a table entry (rule 1; 0 for rule 0); may be NULL
+ * HOST pointers.
+ */
+int mipx_branch_score_batch(mipx_ctx *ctx, int n, int batch, int n_int, const int32_t *int_idx,
+                            const double *x, const int32_t *status, int rule, const double *cost_l,
+                            const double *cost_r, const uint8_t *has_entry, int32_t *branch_idx,
+                            int32_t *mip_feasible, int32_t *n_unprobed);
+/* The same on DEVICE pointers (mipx_dev_alloc), e.g. the x and status of a mipx_lp_solve_batch_dev on
+ * the same stream; asynchronous on the context stream.  int_idx must hold indices in [0, n); the
+ * outputs are all required. */
+int mipx_branch_score_batch_dev(mipx_ctx *ctx, int n, int batch, int n_int, const int32_t *int_idx,
+                                const double *x, const int32_t *status, int rule, const double *cost_l,
+                                const double *cost_r, const uint8_t *has_entry, int32_t *branch_idx,
+                                int32_t *mip_feasible, int32_t *n_unprobed);
+
 /* Device memory owned by the library, for the device-resident entry points. */
 int mipx_dev_alloc(mipx_ctx *ctx, size_t bytes, void **dptr);
 int mipx_dev_free(mipx_ctx *ctx, void *dptr);

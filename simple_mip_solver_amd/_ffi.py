@@ -20,7 +20,7 @@ SYMBOLS = [
     'mipx_last_error', 'mipx_ctx_sync', 'mipx_problem_create', 'mipx_problem_destroy', 'mipx_problem_set_anchor',
     'mipx_tree_set_anchor_mode',
     'mipx_lp_solve_batch', 'mipx_lp_solve_batch_dev', 'mipx_lp_solve_multi', 'mipx_gomory_batch', 'mipx_cut_select_batch',
-    'mipx_safe_cut_batch', 'mipx_get_fraction_batch', 'mipx_lp_solve_batch_cuts', 'mipx_tree_create_ex',
+    'mipx_safe_cut_batch', 'mipx_get_fraction_batch', 'mipx_branch_score_batch', 'mipx_branch_score_batch_dev', 'mipx_lp_solve_batch_cuts', 'mipx_tree_create_ex',
     'mipx_tree_cut_stats', 'mipx_comm_unique_id', 'mipx_comm_create_rccl', 'mipx_comm_create_custom',
     'mipx_comm_destroy', 'mipx_comm_rank', 'mipx_comm_size', 'mipx_comm_allgather', 'mipx_comm_barrier',
     'mipx_tree_set_comm', 'mipx_tree_global_stats', 'mipx_exchange_record_len', 'mipx_exchange_decide',
@@ -429,6 +429,36 @@ def get_fraction_batch(ctx, x, max_term, estimate):
     rc = L.mipx_get_fraction_batch(ctx._h, len(x), _ptr(x), _ptr(mt), _ptr(est), _ptr(num), _ptr(den))
     ctx.check(rc, 'mipx_get_fraction_batch')
     return num.astype(np.int64), den.astype(np.int64)
+
+
+def branch_score_batch(ctx, integer_indices, x, status, rule=0, cost_l=None, cost_r=None, has_entry=None):
+    """K4 on host buffers (mipx_branch_score_batch): x (batch, n), status (batch,) Clp codes, rule 0 most
+    fractional / 1 pseudo cost (then cost_l, cost_r, has_entry: n each).  Returns dict of batch arrays
+    branch_idx (-1: none), mip_feasible (bool), n_unprobed."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    B, n = x.shape
+    ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+    st = np.ascontiguousarray(status, dtype=np.int32).reshape(B)
+    cl = None if cost_l is None else np.ascontiguousarray(cost_l, np.float64).reshape(n)
+    cr = None if cost_r is None else np.ascontiguousarray(cost_r, np.float64).reshape(n)
+    he = None if has_entry is None else np.ascontiguousarray(has_entry, np.uint8).reshape(n)
+    bidx = np.zeros(B, np.int32); mipf = np.zeros(B, np.int32); nun = np.zeros(B, np.int32)
+    L = lib()
+    L.mipx_branch_score_batch.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] * 6
+    rc = L.mipx_branch_score_batch(ctx._h, n, B, len(ii), _ptr(ii), _ptr(x), _ptr(st), int(rule), _ptr(cl),
+                                   _ptr(cr), _ptr(he), _ptr(bidx), _ptr(mipf), _ptr(nun))
+    ctx.check(rc, 'mipx_branch_score_batch')
+    return dict(branch_idx=bidx, mip_feasible=mipf.astype(bool), n_unprobed=nun)
+
+
+def branch_score_batch_dev(ctx, n, B, n_int, d_int_idx, d_x, d_status, rule, d_cost_l, d_cost_r, d_has_entry,
+                           d_branch_idx, d_mip_feasible, d_n_unprobed):
+    """mipx_branch_score_batch_dev: device pointers, asynchronous on the context stream."""
+    L = lib()
+    L.mipx_branch_score_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] * 6
+    rc = L.mipx_branch_score_batch_dev(ctx._h, int(n), int(B), int(n_int), d_int_idx, d_x, d_status, int(rule),
+                                       d_cost_l, d_cost_r, d_has_entry, d_branch_idx, d_mip_feasible, d_n_unprobed)
+    ctx.check(rc, 'mipx_branch_score_batch_dev')
 
 
 def solve_multi(ctx, A, b, c, l, u, max_iter=0):

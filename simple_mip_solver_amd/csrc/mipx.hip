@@ -949,6 +949,74 @@ int mipx_get_fraction_batch(mipx_ctx *ctx, int count, const double *x, const dou
     return MIPX_OK;
 }
 
+int mipx_branch_score_batch_dev(mipx_ctx *ctx, int n, int batch, int n_int, const int32_t *int_idx,
+                                const double *x, const int32_t *status, int rule, const double *cost_l,
+                                const double *cost_r, const uint8_t *has_entry, int32_t *branch_idx,
+                                int32_t *mip_feasible, int32_t *n_unprobed) {
+    if (!ctx || n <= 0 || batch < 0 || n_int < 0 || (rule != 0 && rule != 1) ||
+        (batch && (!x || !status || !branch_idx || !mip_feasible || !n_unprobed)) || (n_int && !int_idx) ||
+        (rule == 1 && (!cost_l || !cost_r || !has_entry)))
+        return fail(ctx, MIPX_EINVAL, "mipx_branch_score_batch_dev: bad argument");
+    if (batch == 0) return MIPX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    mipx::ScoreArgs s{};
+    s.n = n; s.n_int = n_int; s.batch = batch; s.rule = rule;
+    s.int_idx = int_idx; s.x = x; s.status = status;
+    s.cost_l = cost_l; s.cost_r = cost_r; s.has_entry = has_entry;
+    s.branch_idx = branch_idx; s.branch_val = nullptr; s.mip_feasible = mip_feasible;
+    s.n_probe = n_unprobed; s.probe_list = nullptr;
+    s.ask_count = nullptr; s.ask_cap = 0; s.ask_nodes = 0; s.ask = nullptr;
+    hipLaunchKernelGGL(mipx::branch_score, dim3(batch), dim3(64), 0, ctx->stream, s);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
+int mipx_branch_score_batch(mipx_ctx *ctx, int n, int batch, int n_int, const int32_t *int_idx,
+                            const double *x, const int32_t *status, int rule, const double *cost_l,
+                            const double *cost_r, const uint8_t *has_entry, int32_t *branch_idx,
+                            int32_t *mip_feasible, int32_t *n_unprobed) {
+    if (!ctx || n <= 0 || batch < 0 || n_int < 0 || (rule != 0 && rule != 1) ||
+        (batch && (!x || !status || !branch_idx || !mip_feasible)) || (n_int && !int_idx) ||
+        (rule == 1 && (!cost_l || !cost_r || !has_entry)))
+        return fail(ctx, MIPX_EINVAL, "mipx_branch_score_batch: bad argument");
+    for (int k = 0; k < n_int; k++)
+        if (int_idx[k] < 0 || int_idx[k] >= n) return fail(ctx, MIPX_EINVAL, "mipx_branch_score_batch: int_idx out of range");
+    if (batch == 0) return MIPX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, nn = (size_t)n, ni = (size_t)(n_int ? n_int : 1);
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    const size_t o_ii = carve(ni * 4), o_x = carve(B * nn * 8), o_st = carve(B * 4), o_cl = carve(nn * 8),
+                 o_cr = carve(nn * 8), o_he = carve(nn), o_bi = carve(B * 4), o_mf = carve(B * 4), o_np = carve(B * 4);
+    if (off > ctx->scratch_bytes) {
+        if (ctx->scratch) (void)hipFree(ctx->scratch);
+        ctx->scratch = nullptr;
+        ctx->scratch_bytes = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->scratch, off));
+        ctx->scratch_bytes = off;
+    }
+    char *base = (char *)ctx->scratch;
+    hipStream_t st = ctx->stream;
+    if (n_int) HIP_TRY(ctx, hipMemcpyAsync(base + o_ii, int_idx, (size_t)n_int * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_x, x, B * nn * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_st, status, B * 4, hipMemcpyHostToDevice, st));
+    if (rule == 1) {
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_cl, cost_l, nn * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_cr, cost_r, nn * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_he, has_entry, nn, hipMemcpyHostToDevice, st));
+    }
+    int rc = mipx_branch_score_batch_dev(
+        ctx, n, batch, n_int, (const int32_t *)(base + o_ii), (const double *)(base + o_x),
+        (const int32_t *)(base + o_st), rule, (const double *)(base + o_cl), (const double *)(base + o_cr),
+        (const uint8_t *)(base + o_he), (int32_t *)(base + o_bi), (int32_t *)(base + o_mf), (int32_t *)(base + o_np));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(branch_idx, base + o_bi, B * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(mip_feasible, base + o_mf, B * 4, hipMemcpyDeviceToHost, st));
+    if (n_unprobed) HIP_TRY(ctx, hipMemcpyAsync(n_unprobed, base + o_np, B * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return MIPX_OK;
+}
+
 int mipx_dev_alloc(mipx_ctx *ctx, size_t bytes, void **dptr) {
     if (!ctx || !dptr) return MIPX_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -21,10 +21,10 @@ struct ScoreArgs {
     const double *cost_l, *cost_r;  // n (pseudo-cost table by variable)
     const uint8_t *has_entry;       // n
     int32_t *branch_idx;            // batch: variable to branch on or -1
-    double *branch_val;             // batch: x[branch_idx] (b_val of the children)
+    double *branch_val;             // batch: x[branch_idx] (b_val of the children); may be nullptr
     int32_t *mip_feasible;          // batch
     int32_t *n_probe;               // batch
-    int32_t *probe_list;            // batch x n_int (ascending position in int_idx)
+    int32_t *probe_list;            // batch x n_int (ascending position in int_idx); may be nullptr
     // compact copy of the probe requests for the host (read with the step's single D2H): one
     // entry per (node, unprobed fractional variable), a node's entries contiguous and ascending;
     // ask_count may exceed ask_cap (then nothing past the cap is written and the host falls back
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(64) void branch_score(ScoreArgs g) {
             }
         }
         const unsigned long long mask = __ballot(need_probe);
-        if (need_probe)
+        if (need_probe && g.probe_list != nullptr)
             g.probe_list[(size_t)node * g.n_int + nprobe + __popcll(mask & ((1ull << lane) - 1ull))] = k;
         nprobe += __popcll(mask);
     }
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(64) void branch_score(ScoreArgs g) {
         g.mip_feasible[node] = wmax <= kVarEps;
         const int bvar = win == kNoCand ? -1 : g.int_idx[win];
         g.branch_idx[node] = bvar;
-        g.branch_val[node] = bvar < 0 ? 0.0 : x[bvar];
+        if (g.branch_val != nullptr) g.branch_val[node] = bvar < 0 ? 0.0 : x[bvar];
         g.n_probe[node] = nprobe;
     }
     if (g.ask != nullptr && nprobe > 0 && node < g.ask_nodes) {  // wave-uniform; rare once the table has filled

@@ -186,6 +186,12 @@ class LPBackend:
         selection kernel."""
         return None
 
+    def branch_score(self, integer_indices, x, status):
+        """Integrality test and most-fractional index of `batch` solved nodes (x: batch x n, status:
+        batch Clp codes): dict of batch arrays branch_idx (-1: none) and mip_feasible, or None if the
+        engine has no scoring kernel (the nodes then use their host arithmetic)."""
+        return None
+
 
 class HipBackend(LPBackend):
     """Sends the solve to libmipx.so on the MI355X (no fallback)."""
@@ -234,6 +240,10 @@ class HipBackend(LPBackend):
         return _ffi.select_cuts(self._context(), pi, pi0, x, max_nonzero_coefs, min_cut_depth,
                                 cos_parallel, max_abs_coef)
 
+    def branch_score(self, integer_indices, x, status):
+        from simple_mip_solver_amd import _ffi
+        return _ffi.branch_score_batch(self._context(), integer_indices, x, status, rule=0)
+
 
 _backend = None
 
@@ -263,6 +273,27 @@ class _RowSet:
         self.c = np.ascontiguousarray(c, dtype=np.float64)
         _RowSet._next_key += 1
         self.key = _RowSet._next_key
+        self.rowidx = None   # (LP row position, is a >= side) per engine row; DenseLP._row_index
+
+
+class Prefetch:
+    """A node LP result solved ahead of `dual()` in a batch (BranchAndBound(lp_batch=...)), with what
+    it was solved from.  `dual()` consumes it at most once, and only if the LP still matches."""
+
+    __slots__ = ('res', 'k', 'key', 'max_iter', 'warm', 'l', 'u', 'score', 'stats', 'used')
+
+    def __init__(self, res, k, key, max_iter, warm, l, u, score, stats):
+        self.res, self.k, self.key, self.max_iter = res, k, key, max_iter
+        self.warm, self.l, self.u = warm, l, u
+        self.score = score   # (branch index or None, mip_feasible) from the engine's K4, or None
+        self.stats = stats   # dict with 'consumed' / 'wasted' counters
+        self.used = False
+
+    def matches(self, key, max_iter, warm, l, u):
+        if key != self.key or max_iter != self.max_iter or (warm is None) != (self.warm is None):
+            return False
+        return (warm is None or np.array_equal(warm, self.warm)) and \
+            np.array_equal(l, self.l) and np.array_equal(u, self.u)
 
 
 class DenseLP:
@@ -288,6 +319,8 @@ class DenseLP:
         self._rowset = None       # cached engine form of the rows
         self._rowmap = None       # (constraint index, row in block, sign) per engine row
         self._solved_sig = None   # what the stored optimal solution belongs to (see dual())
+        self._prefetched = None   # a Prefetch waiting for dual()
+        self._score = None        # engine scan of the stored solution, when it came from a Prefetch
 
     # ---- model building ------------------------------------------------------------------
     def addVariable(self, name, dim):
@@ -442,20 +475,32 @@ class DenseLP:
         u = np.where(self.variablesUpper >= COIN_INFINITY / 2, np.inf, self.variablesUpper)
         return l.astype(np.float64), u.astype(np.float64)
 
+    def _row_index(self):
+        """(position in the LP's rows, is the >= side) of every engine row, as index arrays built once
+        per row map and kept on the row set (which children share with their parent)."""
+        rs = self._rowset
+        if rs.rowidx is None:
+            offsets = np.cumsum([0] + [c.rows for c in self.constraints])
+            rm = self._rowmap
+            ci = np.fromiter((e[0] for e in rm), np.intp, len(rm))
+            r = np.fromiter((e[1] for e in rm), np.intp, len(rm))
+            sign = np.fromiter((e[2] for e in rm), np.float64, len(rm))
+            rs.rowidx = (offsets[ci] + r, sign > 0)
+        return rs.rowidx
+
     def _warm_start(self, rowset):
         """Engine status vector (n structural + one per engine row) or None for a cold start."""
         if self._var_status is None:
             return None
-        n = self.nVariables
-        offsets = np.cumsum([0] + [c.rows for c in self.constraints])
-        rstat = np.ones(len(self._rowmap), np.int8)
-        for k, (ci, r, sign) in enumerate(self._rowmap):
-            code = self._row_status[offsets[ci] + r] if self._row_status is not None else 1
+        pos, plus = self._row_index()
+        if self._row_status is not None:
+            code = self._row_status[pos]
             # Clp's row status refers to the row activity: "at upper" of a <= row is its slack at 0;
             # of the two engine rows of a ranged / equality row only the tight side is nonbasic
-            tight = (code == 3 and sign > 0) or (code == 2 and sign < 0) or \
-                    (code not in (1, 2, 3))
-            rstat[k] = 3 if tight else 1
+            tight = np.where(plus, code == 3, code == 2) | ((code != 1) & (code != 2) & (code != 3))
+            rstat = np.where(tight, 3, 1).astype(np.int8)
+        else:
+            rstat = np.ones(len(pos), np.int8)
         return np.concatenate([self._var_status.astype(np.int8), rstat])[None]
 
     def dual(self):
@@ -472,6 +517,19 @@ class DenseLP:
         if sig is not None and self._status == 0 and sig[0] == rs.key and sig[1] == max_iter and \
                 sig[2] is self._var_status and np.array_equal(sig[3], l) and np.array_equal(sig[4], u):
             return self._status
+        pre = self._prefetched
+        if pre is not None:
+            # solved ahead in a batch: take it if it was solved from exactly this LP (at most once)
+            self._prefetched = None
+            pre.used = True
+            warm = self._warm_start(rs)
+            if pre.matches(rs.key, max_iter, warm, l, u):
+                pre.stats['consumed'] += 1
+                self._store(pre.res, pre.k)
+                self._score = pre.score
+                self._solved_sig = (rs.key, max_iter, self._var_status, l, u)
+                return self._status
+            pre.stats['wasted'] += 1
         res = get_backend().solve(rs.A, rs.b, rs.c, l[None], u[None], self._warm_start(rs),
                                   max_iter, rs.key)
         self._store(res, 0)
@@ -559,16 +617,20 @@ class DenseLP:
         self.iteration = int(res['iters'][k])
         vs = np.asarray(res['vstat'][k], dtype=np.int8)
         self._var_status = vs[:n].copy()
-        offsets = np.cumsum([0] + [c.rows for c in self.constraints])
+        self._score = None
+        pos, plus = self._row_index()
+        minus = ~plus
         row_status = np.ones(self.nConstraints, np.int8)
         duals = np.zeros(self.nConstraints)
         y = np.asarray(res['y'][k], dtype=np.float64)
-        for e, (ci, r, sign) in enumerate(self._rowmap):
-            pos = offsets[ci] + r
-            if vs[n + e] != 1:
-                # slack at zero: the row is tight at its lower (>= row) or upper (<= row) side
-                row_status[pos] = 3 if sign > 0 else 2
-            duals[pos] += sign * y[e]
+        # slack at zero: the row is tight at its lower (>= row) or upper (<= row) side.  A ranged row's
+        # <= side follows its >= side in the row map, so it is written second, as a row-by-row loop would;
+        # within one side every LP row occurs once
+        tight = vs[n:n + len(pos)] != 1
+        row_status[pos[tight & plus]] = 3
+        row_status[pos[tight & minus]] = 2
+        duals[pos[plus]] += y[:len(pos)][plus]
+        duals[pos[minus]] += -y[:len(pos)][minus]
         self._row_status = row_status
         self._row_duals = duals
         # reduced costs of the columns: d = c - A'y over the engine's rows

@@ -215,7 +215,10 @@ class BaseNode:
         sol = self.lp.primalVariableSolution
         self.solution = None if not self.lp_feasible else \
             sol['x'] if isinstance(sol, dict) else sol
-        if self.lp_feasible:
+        scan = self._engine_scan()
+        if scan is not None and self.lp_feasible:
+            self.mip_feasible = scan[1]
+        elif self.lp_feasible:
             ints = self.solution[self._int_idx]
             self.mip_feasible = bool(np.max(np.abs(np.round(ints) - ints)) <= tol.variable_epsilon) \
                 if ints.size else True
@@ -458,10 +461,28 @@ class BaseNode:
         None when all are integral or nothing is solved (reference :544-562)."""
         if not self.lp_feasible or not self._int_idx.size:
             return None
+        scan = self._engine_scan()
+        if scan is not None:
+            return scan[0]
         x = self.solution[self._int_idx]
         dist = np.minimum(x - np.floor(x), np.ceil(x) - x)
         k = int(np.argmax(dist))  # first maximum == the reference's strict '>' scan
         return self._integer_indices[k] if dist[k] > tol.variable_epsilon else None
+
+    def _engine_scan(self):
+        """(most fractional index or None, mip_feasible) of `solution` as the engine's K4 computed them
+        beside a batched solve (BranchAndBound(lp_batch=...)), or None: when the solution is not that
+        prefetched one, or when this class brings its own integrality rules."""
+        score = self.lp._score
+        if score is None or self.solution is None or self.solution is not self.lp._x:
+            return None
+        cls = type(self)
+        if cls._most_fractional_index is not BaseNode._most_fractional_index or \
+                cls._is_fractional is not BaseNode._is_fractional or \
+                cls._fractional_indices is not BaseNode._fractional_indices or \
+                '_is_fractional' in self.__dict__ or '_fractional_indices' in self.__dict__:
+            return None
+        return score
 
     def _base_branch(self, branch_idx, next_node_idx=None, **kwargs):
         """Children with x[branch_idx] <= floor / >= ceil, warm-started from this node's basis
