@@ -20,6 +20,7 @@
  *   - Every function returns 0 on success or a negative MIPX_E* code; nothing throws across
  *     the ABI; mipx_last_error() returns a description of the last failure on that context.
  *   - Host buffers stay owned by the caller; the library keeps no host pointer past return.
+ *     Every host-buffer entry point syncs its stream before it returns, on error too.
  *   - A context is bound to one GPU and one HIP stream and is not thread-safe.
  *   - There is NO CPU fallback: without a usable gfx950 device mipx_ctx_create fails.
  */

@@ -14,28 +14,6 @@ MIPX_OK = 0
 ERRORS = {-1: 'MIPX_EINVAL', -2: 'MIPX_ENODEV', -3: 'MIPX_EHIP', -4: 'MIPX_ETOOBIG',
           -5: 'MIPX_ENOMEM', -6: 'MIPX_EHOOK', -7: 'MIPX_EPEER'}
 
-# every symbol include/mipx.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    'mipx_abi_version', 'mipx_device_count', 'mipx_ctx_create', 'mipx_ctx_destroy',
-    'mipx_last_error', 'mipx_ctx_sync', 'mipx_problem_create', 'mipx_problem_destroy', 'mipx_problem_set_anchor',
-    'mipx_tree_set_anchor_mode',
-    'mipx_lp_solve_batch', 'mipx_lp_solve_batch_dev', 'mipx_lp_solve_multi', 'mipx_gomory_batch', 'mipx_cut_select_batch',
-    'mipx_safe_cut_batch', 'mipx_get_fraction_batch', 'mipx_branch_score_batch', 'mipx_branch_score_batch_dev', 'mipx_lp_solve_batch_cuts', 'mipx_tree_create_ex',
-    'mipx_tree_cut_stats', 'mipx_comm_unique_id', 'mipx_comm_create_rccl', 'mipx_comm_create_custom',
-    'mipx_comm_destroy', 'mipx_comm_rank', 'mipx_comm_size', 'mipx_comm_allgather', 'mipx_comm_barrier',
-    'mipx_tree_set_comm', 'mipx_tree_global_stats', 'mipx_exchange_record_len', 'mipx_exchange_decide',
-    'mipx_tree_exchange_record', 'mipx_tree_trace_cuts', 'mipx_tree_peek_cuts', 'mipx_tree_cut_store',
-    'mipx_tree_cut_rows_per_node', 'mipx_tree_migrate_self', 'mipx_tree_kernel_ms', 'mipx_last_kernel_ms',
-    'mipx_dev_alloc', 'mipx_dev_free',
-    'mipx_memcpy_h2d', 'mipx_memcpy_d2h', 'mipx_timer_start', 'mipx_timer_stop',
-    'mipx_kernel_name', 'mipx_debug_enable', 'mipx_debug_read',
-    'mipx_tree_create', 'mipx_tree_destroy', 'mipx_tree_solve', 'mipx_tree_get_stats',
-    'mipx_tree_solution', 'mipx_tree_set_primal_bound', 'mipx_tree_pseudo_costs', 'mipx_tree_set_pseudo_costs',
-    'mipx_tree_set_trace', 'mipx_tree_trace', 'mipx_tree_peek_open', 'mipx_tree_keep_shard',
-    'mipx_tree_set_step_hook', 'mipx_lp_dive_batch', 'mipx_lp_plunge_batch', 'mipx_tree_set_dive', 'mipx_tree_reanchor',
-    'mipx_tree_peek_anchors', 'mipx_tree_anchor_table',
-]
-
 _dp = C.POINTER(C.c_double)
 _i8p = C.POINTER(C.c_int8)
 _i32p = C.POINTER(C.c_int32)
@@ -114,9 +92,7 @@ def exchange_decide(records, n, mip_gap=1e-4, allow_migration=True):
     world = records.shape[0]
     assert records.shape[1] == exchange_record_len(n)
     d = ExchangeDecision()
-    L = lib()
-    L.mipx_exchange_decide.argtypes = [C.c_int, C.c_int, _vp, C.c_double, C.c_int, C.POINTER(ExchangeDecision)]
-    rc = L.mipx_exchange_decide(world, int(n), _ptr(records), float(mip_gap), int(bool(allow_migration)), C.byref(d))
+    rc = lib().mipx_exchange_decide(world, int(n), _ptr(records), float(mip_gap), int(bool(allow_migration)), C.byref(d))
     if rc != MIPX_OK:
         raise MipxError(f'mipx_exchange_decide failed: {ERRORS.get(rc, rc)}')
     return dict(primal=d.primal, dual=d.dual, gap=None if d.gap < 0 else d.gap, sums=list(d.sums),
@@ -136,6 +112,88 @@ TREE_STATUS = {0: 'unsolved', 1: 'optimal', 2: 'infeasible', 3: 'unbounded',
                4: 'stopped on iterations or time'}
 
 
+TREE_HOOK = C.CFUNCTYPE(C.c_int, _vp)   # mipx_tree_hook
+
+_i, _i64, _d, _sz = C.c_int, C.c_int64, C.c_double, C.c_size_t
+_fp, _pvp = C.POINTER(C.c_float), C.POINTER(_vp)
+
+# (restype, argtypes) of every function include/mipx.h declares, in its order; lib() applies them once
+# (tests/test_abi.py checks them against the header's prototypes)
+_SIGNATURES = {
+    'mipx_abi_version': (_i, []),
+    'mipx_device_count': (_i, []),
+    'mipx_ctx_create': (_i, [_i, _pvp]),
+    'mipx_ctx_destroy': (None, [_vp]),
+    'mipx_last_error': (C.c_char_p, [_vp]),
+    'mipx_ctx_sync': (_i, [_vp]),
+    'mipx_problem_create': (_i, [_vp, _i, _i, _dp, _dp, _dp, _pvp]),
+    'mipx_problem_destroy': (None, [_vp]),
+    'mipx_lp_dive_batch': (_i, [_vp, _i] + [_vp] * 3 + [_i, _i, _vp, _i] + [_vp] * 3 + [_d] + [_vp] * 9),
+    'mipx_lp_plunge_batch': (_i, [_vp, _i, _i] + [_vp] * 3 + [_i, _i, _vp, _i] + [_vp] * 3 + [_d] + [_vp] * 9),
+    'mipx_problem_set_anchor': (_i, [_vp, _vp]),
+    'mipx_lp_solve_batch': (_i, [_vp, _i] + [_vp] * 3 + [_i] + [_vp] * 7),
+    'mipx_lp_solve_batch_cuts': (_i, [_vp, _i] + [_vp] * 3 + [_i, _vp, _vp, _i, _vp, _vp, _i] + [_vp] * 7),
+    'mipx_lp_solve_batch_dev': (_i, [_vp, _i] + [_vp] * 3 + [_i] + [_vp] * 7),
+    'mipx_lp_solve_multi': (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [_i] + [_vp] * 6),
+    'mipx_gomory_batch': (_i, [_vp, _i] + [_vp] * 5 + [_d] + [_vp] * 6),
+    'mipx_cut_select_batch': (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [_i, _d, _d, _d] + [_vp] * 4),
+    'mipx_safe_cut_batch': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _d] + [_vp] * 7),
+    'mipx_get_fraction_batch': (_i, [_vp, _i] + [_vp] * 5),
+    'mipx_branch_score_batch': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 6),
+    'mipx_branch_score_batch_dev': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 6),
+    'mipx_dev_alloc': (_i, [_vp, _sz, _pvp]),
+    'mipx_dev_free': (_i, [_vp, _vp]),
+    'mipx_memcpy_h2d': (_i, [_vp, _vp, _vp, _sz]),
+    'mipx_memcpy_d2h': (_i, [_vp, _vp, _vp, _sz]),
+    'mipx_timer_start': (_i, [_vp]),
+    'mipx_timer_stop': (_i, [_vp, _fp]),
+    'mipx_debug_enable': (_i, [_vp]),
+    'mipx_debug_read': (_i, [_vp, _vp, _vp, _vp]),
+    'mipx_tree_create': (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i64, _pvp]),
+    'mipx_tree_create_ex': (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i64, C.POINTER(CutParams), _pvp]),
+    'mipx_tree_cut_stats': (_i, [_vp, _vp]),
+    'mipx_tree_destroy': (None, [_vp]),
+    'mipx_tree_solve': (_i, [_vp, _i64, _d, _d, _i, _i64, C.POINTER(TreeStats)]),
+    'mipx_tree_get_stats': (_i, [_vp, C.POINTER(TreeStats)]),
+    'mipx_tree_solution': (_i, [_vp, _vp]),
+    'mipx_tree_set_primal_bound': (_i, [_vp, _d]),
+    'mipx_tree_set_anchor_mode': (_i, [_vp, _i]),
+    'mipx_tree_pseudo_costs': (_i, [_vp] + [_vp] * 4),
+    'mipx_tree_set_pseudo_costs': (_i, [_vp] + [_vp] * 4),
+    'mipx_tree_reanchor': (_i, [_vp, _i64]),
+    'mipx_tree_peek_anchors': (_i64, [_vp, _i64, _vp]),
+    'mipx_tree_anchor_table': (_i64, [_vp, _vp, _vp, _vp]),
+    'mipx_tree_set_dive': (_i, [_vp, _i]),
+    'mipx_tree_set_step_hook': (_i, [_vp, TREE_HOOK, _vp, _i]),
+    'mipx_tree_peek_open': (_i64, [_vp, _i64] + [_vp] * 4),
+    'mipx_tree_keep_shard': (_i, [_vp, _i, _i]),
+    'mipx_tree_set_trace': (_i, [_vp, _i]),
+    'mipx_tree_trace': (_i64, [_vp, _i64] + [_vp] * 4),
+    'mipx_tree_kernel_ms': (_i, [_vp, _vp]),
+    'mipx_tree_trace_cuts': (_i64, [_vp, _i64, _vp]),
+    'mipx_tree_peek_cuts': (_i64, [_vp, _i64] + [_vp] * 4),
+    'mipx_tree_cut_store': (_i64, [_vp, _i64, _vp, _vp]),
+    'mipx_tree_cut_rows_per_node': (_i, [_vp]),
+    'mipx_comm_unique_id': (_i, [C.c_char_p]),
+    'mipx_comm_create_rccl': (_i, [_vp, C.c_char_p, _i, _i, _pvp]),
+    'mipx_comm_create_custom': (_i, [_vp, _i, _i, C.POINTER(CommOps), _vp, _pvp]),
+    'mipx_comm_destroy': (None, [_vp]),
+    'mipx_comm_rank': (_i, [_vp]),
+    'mipx_comm_size': (_i, [_vp]),
+    'mipx_comm_allgather': (_i, [_vp, _vp, _vp, _sz]),
+    'mipx_comm_barrier': (_i, [_vp]),
+    'mipx_tree_set_comm': (_i, [_vp, _vp, _i]),
+    'mipx_exchange_record_len': (_i, [_i]),
+    'mipx_exchange_decide': (_i, [_i, _i, _vp, _d, _i, C.POINTER(ExchangeDecision)]),
+    'mipx_tree_migrate_self': (_i64, [_vp, _i64]),
+    'mipx_tree_exchange_record': (_i, [_vp, _vp]),
+    'mipx_tree_global_stats': (_i, [_vp, C.POINTER(GlobalStats)]),
+    'mipx_last_kernel_ms': (_i, [_vp, _fp]),
+    'mipx_kernel_name': (_i, [_i, _i, C.c_char_p, _sz]),
+}
+SYMBOLS = list(_SIGNATURES)   # (tests/test_abi.py: the header declares exactly these)
+
+
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
     global _lib
@@ -147,49 +205,9 @@ def lib():
             f'(run `make -C {os.path.dirname(LIB_PATH)}` or __graft_entry__.build()). '
             'simple_mip_solver_amd has no CPU fallback.')
     L = C.CDLL(LIB_PATH)
-    L.mipx_abi_version.restype = C.c_int
-    L.mipx_device_count.restype = C.c_int
-    L.mipx_ctx_create.argtypes = [C.c_int, C.POINTER(_vp)]
-    L.mipx_ctx_destroy.argtypes = [_vp]
-    L.mipx_ctx_destroy.restype = None
-    L.mipx_last_error.argtypes = [_vp]
-    L.mipx_last_error.restype = C.c_char_p
-    L.mipx_ctx_sync.argtypes = [_vp]
-    L.mipx_problem_create.argtypes = [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(_vp)]
-    L.mipx_problem_destroy.argtypes = [_vp]
-    L.mipx_problem_set_anchor.argtypes = [_vp, _vp]
-    L.mipx_tree_set_anchor_mode.argtypes = [_vp, C.c_int]
-    L.mipx_problem_destroy.restype = None
-    solve_args = [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.mipx_lp_solve_batch.argtypes = solve_args
-    L.mipx_lp_solve_batch_dev.argtypes = solve_args
-    L.mipx_lp_solve_multi.argtypes = [_vp, C.c_int, C.c_int, C.c_int] + [_vp] * 5 + [C.c_int] + [_vp] * 6
-    L.mipx_gomory_batch.argtypes = [_vp, C.c_int] + [_vp] * 5 + [C.c_double] + [_vp] * 6
-    L.mipx_cut_select_batch.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int,
-                                        C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]
-    L.mipx_dev_alloc.argtypes = [_vp, C.c_size_t, C.POINTER(_vp)]
-    L.mipx_dev_free.argtypes = [_vp, _vp]
-    L.mipx_memcpy_h2d.argtypes = [_vp, _vp, _vp, C.c_size_t]
-    L.mipx_memcpy_d2h.argtypes = [_vp, _vp, _vp, C.c_size_t]
-    L.mipx_timer_start.argtypes = [_vp]
-    L.mipx_timer_stop.argtypes = [_vp, C.POINTER(C.c_float)]
-    L.mipx_kernel_name.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_size_t]
-    L.mipx_tree_create.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   C.c_int64, C.POINTER(_vp)]
-    L.mipx_tree_destroy.argtypes = [_vp]
-    L.mipx_tree_destroy.restype = None
-    L.mipx_tree_solve.argtypes = [_vp, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int64,
-                                  C.POINTER(TreeStats)]
-    L.mipx_tree_get_stats.argtypes = [_vp, C.POINTER(TreeStats)]
-    L.mipx_tree_solution.argtypes = [_vp, _vp]
-    L.mipx_tree_set_primal_bound.argtypes = [_vp, C.c_double]
-    L.mipx_tree_pseudo_costs.argtypes = [_vp, _vp, _vp, _vp, _vp]
-    L.mipx_tree_set_trace.argtypes = [_vp, C.c_int]
-    L.mipx_tree_trace.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp]
-    L.mipx_tree_trace.restype = C.c_int64
-    L.mipx_tree_peek_open.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp]
-    L.mipx_tree_peek_open.restype = C.c_int64
-    L.mipx_tree_keep_shard.argtypes = [_vp, C.c_int, C.c_int]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -198,12 +216,15 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(_vp)
 
 
+def _arr(a, dtype, shape=-1):
+    """An optional input array as a contiguous `dtype` array of `shape` (None stays None)."""
+    return None if a is None else np.ascontiguousarray(a, dtype).reshape(shape)
+
+
 def comm_unique_id():
     """The 128 bytes rank 0 makes (ncclGetUniqueId) and the launcher hands to every rank."""
     buf = C.create_string_buffer(128)
-    L = lib()
-    L.mipx_comm_unique_id.argtypes = [C.c_char_p]
-    rc = L.mipx_comm_unique_id(buf)
+    rc = lib().mipx_comm_unique_id(buf)
     if rc != MIPX_OK:
         raise MipxError(f'mipx_comm_unique_id failed: {ERRORS.get(rc, rc)} (librccl.so is needed for more than one GPU)')
     return buf.raw
@@ -219,12 +240,10 @@ class Comm:
 
     def __init__(self, ctx, rank, world, unique_id=None, allgather=None, send=None, recv=None):
         self.ctx, self.rank, self.world = ctx, int(rank), int(world)
-        L = lib()
         h = _vp()
         if unique_id is not None:
             assert len(unique_id) == 128, 'the RCCL unique id has 128 bytes'
-            L.mipx_comm_create_rccl.argtypes = [_vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(_vp)]
-            rc = L.mipx_comm_create_rccl(ctx._h, unique_id, self.rank, self.world, C.byref(h))
+            rc = lib().mipx_comm_create_rccl(ctx._h, unique_id, self.rank, self.world, C.byref(h))
             ctx.check(rc, 'mipx_comm_create_rccl')
             self.transport = 'rccl'
         else:
@@ -254,9 +273,8 @@ class Comm:
                 C.memmove(bufp, data, nbytes)
             self._ops = CommOps(CommOps.ALLGATHER(guard(c_allgather)), CommOps.SEND(guard(c_send)),
                                 CommOps.RECV(guard(c_recv)))
-            L.mipx_comm_create_custom.argtypes = [_vp, C.c_int, C.c_int, C.POINTER(CommOps), _vp, C.POINTER(_vp)]
-            rc = L.mipx_comm_create_custom(None if ctx is None else ctx._h, self.rank, self.world,
-                                           C.byref(self._ops), None, C.byref(h))
+            rc = lib().mipx_comm_create_custom(None if ctx is None else ctx._h, self.rank, self.world,
+                                               C.byref(self._ops), None, C.byref(h))
             if rc != MIPX_OK:
                 raise MipxError(f'mipx_comm_create_custom failed: {ERRORS.get(rc, rc)}')
             self.transport = 'custom'
@@ -275,22 +293,15 @@ class Comm:
         """All-gather of one equally sized array per rank (host, blocking): (world, ...) array."""
         arr = np.ascontiguousarray(arr)
         out = np.zeros((self.world,) + arr.shape, arr.dtype)
-        L = lib()
-        L.mipx_comm_allgather.argtypes = [_vp, _vp, _vp, C.c_size_t]
-        self.check(L.mipx_comm_allgather(self._h, _ptr(arr), _ptr(out), arr.nbytes), 'mipx_comm_allgather')
+        self.check(lib().mipx_comm_allgather(self._h, _ptr(arr), _ptr(out), arr.nbytes), 'mipx_comm_allgather')
         return out
 
     def barrier(self):
-        L = lib()
-        L.mipx_comm_barrier.argtypes = [_vp]
-        self.check(L.mipx_comm_barrier(self._h), 'mipx_comm_barrier')
+        self.check(lib().mipx_comm_barrier(self._h), 'mipx_comm_barrier')
 
     def close(self):
         if getattr(self, '_h', None) and (self.ctx is None or getattr(self.ctx, '_h', None)):
-            L = lib()
-            L.mipx_comm_destroy.argtypes = [_vp]
-            L.mipx_comm_destroy.restype = None
-            L.mipx_comm_destroy(self._h)
+            lib().mipx_comm_destroy(self._h)
         self._h = None
 
     def __del__(self):
@@ -327,9 +338,7 @@ class Context:
     def last_kernel_ms(self):
         """Device time of the LP launch inside the last solve_multi call (mipx_last_kernel_ms)."""
         ms = C.c_float()
-        L = lib()
-        L.mipx_last_kernel_ms.argtypes = [_vp, C.POINTER(C.c_float)]
-        self.check(L.mipx_last_kernel_ms(self._h, C.byref(ms)), 'mipx_last_kernel_ms')
+        self.check(lib().mipx_last_kernel_ms(self._h, C.byref(ms)), 'mipx_last_kernel_ms')
         return float(ms.value)
 
     def timer_start(self):
@@ -408,11 +417,9 @@ def safe_cut_batch(ctx, pi, pi0, estimate='over', make_integer=False, max_term=1
     spi = np.zeros((B, n)); spi0 = np.zeros(B)
     num = np.zeros((B, n + 1)); den = np.zeros((B, n + 1))
     cpi = np.zeros((B, n)); cpi0 = np.zeros(B); nz = np.zeros(B, np.int32)
-    L = lib()
-    L.mipx_safe_cut_batch.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double] + [_vp] * 7
-    rc = L.mipx_safe_cut_batch(ctx._h, n, B, _ptr(pi), _ptr(pi0), _EST[estimate], int(bool(make_integer)),
-                               float(max_term), _ptr(spi), _ptr(spi0), _ptr(num), _ptr(den), _ptr(cpi),
-                               _ptr(cpi0), _ptr(nz))
+    rc = lib().mipx_safe_cut_batch(ctx._h, n, B, _ptr(pi), _ptr(pi0), _EST[estimate], int(bool(make_integer)),
+                                   float(max_term), _ptr(spi), _ptr(spi0), _ptr(num), _ptr(den), _ptr(cpi),
+                                   _ptr(cpi0), _ptr(nz))
     ctx.check(rc, 'mipx_safe_cut_batch')
     return dict(safe_pi=spi, safe_pi0=spi0, num=num, den=den, scaled_pi=cpi, scaled_pi0=cpi0, nonzero=nz)
 
@@ -424,9 +431,7 @@ def get_fraction_batch(ctx, x, max_term, estimate):
     mt = np.ascontiguousarray(np.broadcast_to(np.asarray(max_term, dtype=np.float64), x.shape))
     est = np.ascontiguousarray([_EST[e] for e in estimate], dtype=np.int32)
     num = np.zeros(len(x)); den = np.zeros(len(x))
-    L = lib()
-    L.mipx_get_fraction_batch.argtypes = [_vp, C.c_int] + [_vp] * 5
-    rc = L.mipx_get_fraction_batch(ctx._h, len(x), _ptr(x), _ptr(mt), _ptr(est), _ptr(num), _ptr(den))
+    rc = lib().mipx_get_fraction_batch(ctx._h, len(x), _ptr(x), _ptr(mt), _ptr(est), _ptr(num), _ptr(den))
     ctx.check(rc, 'mipx_get_fraction_batch')
     return num.astype(np.int64), den.astype(np.int64)
 
@@ -439,14 +444,10 @@ def branch_score_batch(ctx, integer_indices, x, status, rule=0, cost_l=None, cos
     B, n = x.shape
     ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
     st = np.ascontiguousarray(status, dtype=np.int32).reshape(B)
-    cl = None if cost_l is None else np.ascontiguousarray(cost_l, np.float64).reshape(n)
-    cr = None if cost_r is None else np.ascontiguousarray(cost_r, np.float64).reshape(n)
-    he = None if has_entry is None else np.ascontiguousarray(has_entry, np.uint8).reshape(n)
+    cl, cr, he = _arr(cost_l, np.float64, n), _arr(cost_r, np.float64, n), _arr(has_entry, np.uint8, n)
     bidx = np.zeros(B, np.int32); mipf = np.zeros(B, np.int32); nun = np.zeros(B, np.int32)
-    L = lib()
-    L.mipx_branch_score_batch.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] * 6
-    rc = L.mipx_branch_score_batch(ctx._h, n, B, len(ii), _ptr(ii), _ptr(x), _ptr(st), int(rule), _ptr(cl),
-                                   _ptr(cr), _ptr(he), _ptr(bidx), _ptr(mipf), _ptr(nun))
+    rc = lib().mipx_branch_score_batch(ctx._h, n, B, len(ii), _ptr(ii), _ptr(x), _ptr(st), int(rule), _ptr(cl),
+                                       _ptr(cr), _ptr(he), _ptr(bidx), _ptr(mipf), _ptr(nun))
     ctx.check(rc, 'mipx_branch_score_batch')
     return dict(branch_idx=bidx, mip_feasible=mipf.astype(bool), n_unprobed=nun)
 
@@ -454,10 +455,8 @@ def branch_score_batch(ctx, integer_indices, x, status, rule=0, cost_l=None, cos
 def branch_score_batch_dev(ctx, n, B, n_int, d_int_idx, d_x, d_status, rule, d_cost_l, d_cost_r, d_has_entry,
                            d_branch_idx, d_mip_feasible, d_n_unprobed):
     """mipx_branch_score_batch_dev: device pointers, asynchronous on the context stream."""
-    L = lib()
-    L.mipx_branch_score_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] * 6
-    rc = L.mipx_branch_score_batch_dev(ctx._h, int(n), int(B), int(n_int), d_int_idx, d_x, d_status, int(rule),
-                                       d_cost_l, d_cost_r, d_has_entry, d_branch_idx, d_mip_feasible, d_n_unprobed)
+    rc = lib().mipx_branch_score_batch_dev(ctx._h, int(n), int(B), int(n_int), d_int_idx, d_x, d_status, int(rule),
+                                           d_cost_l, d_cost_r, d_has_entry, d_branch_idx, d_mip_feasible, d_n_unprobed)
     ctx.check(rc, 'mipx_branch_score_batch_dev')
 
 
@@ -497,7 +496,7 @@ class Problem:
 
     def set_anchor(self, vstat):
         """Anchor warm starts at the tableau of basis `vstat` (None switches it off)."""
-        v = None if vstat is None else np.ascontiguousarray(vstat, dtype=np.int8).reshape(self.n + self.m)
+        v = _arr(vstat, np.int8, self.n + self.m)
         self.ctx.check(lib().mipx_problem_set_anchor(self._h, _ptr(v)), 'mipx_problem_set_anchor')
 
     def solve_batch(self, l, u, vstat=None, max_iter=0):
@@ -507,8 +506,7 @@ class Problem:
         u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, n)
         B = l.shape[0]
         assert u.shape[0] == B
-        if vstat is not None:
-            vstat = np.ascontiguousarray(vstat, dtype=np.int8).reshape(B, n + m)
+        vstat = _arr(vstat, np.int8, (B, n + m))
         status = np.zeros(B, np.int32)
         obj = np.zeros(B, np.float64)
         x = np.zeros((B, n), np.float64)
@@ -545,12 +543,9 @@ class Problem:
                 vin[k, :n + m + ncut[k]] = vstat[k]
         status = np.zeros(B, np.int32); obj = np.zeros(B); x = np.zeros((B, n)); y = np.zeros((B, M))
         vout = np.zeros((B, n + M), np.int8); iters = np.zeros(B, np.int32); npiv = np.zeros(B, np.int32)
-        L = lib()
-        L.mipx_lp_solve_batch_cuts.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp,
-                                               C.c_int] + [_vp] * 7
-        rc = L.mipx_lp_solve_batch_cuts(self._h, B, _ptr(l), _ptr(u), _ptr(vin), len(cut_pi0), _ptr(cut_pi),
-                                        _ptr(cut_pi0), kc, _ptr(ncut), _ptr(ids), int(max_iter), _ptr(status),
-                                        _ptr(obj), _ptr(x), _ptr(y), _ptr(vout), _ptr(iters), _ptr(npiv))
+        rc = lib().mipx_lp_solve_batch_cuts(self._h, B, _ptr(l), _ptr(u), _ptr(vin), len(cut_pi0), _ptr(cut_pi),
+                                            _ptr(cut_pi0), kc, _ptr(ncut), _ptr(ids), int(max_iter), _ptr(status),
+                                            _ptr(obj), _ptr(x), _ptr(y), _ptr(vout), _ptr(iters), _ptr(npiv))
         self.ctx.check(rc, 'mipx_lp_solve_batch_cuts')
         return dict(status=status, obj=obj, x=x, iters=iters, npivots=npiv,
                     y=[y[k, :m + ncut[k]].copy() for k in range(B)],
@@ -567,24 +562,18 @@ class Problem:
         B = l.shape[0]
         D = int(depth)
         u = np.ascontiguousarray(u, dtype=np.float64).reshape(B, n)
-        if vstat is not None:
-            vstat = np.ascontiguousarray(vstat, dtype=np.int8).reshape(B, n + m)
+        vstat = _arr(vstat, np.int8, (B, n + m))
         ii = np.ascontiguousarray(integer_indices, dtype=np.int32)
-        cl = None if cost_l is None else np.ascontiguousarray(cost_l, np.float64)
-        cr = None if cost_r is None else np.ascontiguousarray(cost_r, np.float64)
-        he = None if has_entry is None else np.ascontiguousarray(has_entry, np.uint8)
+        cl, cr, he = _arr(cost_l, np.float64), _arr(cost_r, np.float64), _arr(has_entry, np.uint8)
         R = (D + 1) * B
         status = np.zeros(R, np.int32); obj = np.zeros(R); x = np.zeros((R, n))
         vout = np.zeros((R, n + m), np.int8); iters = np.zeros(R, np.int32)
         npiv = np.zeros(R, np.int32)
         dvar = np.zeros(D * B, np.int32); ddir = np.zeros(D * B, np.int32); dval = np.zeros(D * B)
-        L = lib()
-        L.mipx_lp_plunge_batch.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int,
-                                           _vp, _vp, _vp, C.c_double] + [_vp] * 9
-        rc = L.mipx_lp_plunge_batch(self._h, B, D, _ptr(l), _ptr(u), _ptr(vstat), int(max_iter), int(rule),
-                                    _ptr(ii), len(ii), _ptr(cl), _ptr(cr), _ptr(he), float(cutoff),
-                                    _ptr(status), _ptr(obj), _ptr(x), _ptr(vout), _ptr(iters), _ptr(npiv),
-                                    _ptr(dvar), _ptr(ddir), _ptr(dval))
+        rc = lib().mipx_lp_plunge_batch(self._h, B, D, _ptr(l), _ptr(u), _ptr(vstat), int(max_iter), int(rule),
+                                        _ptr(ii), len(ii), _ptr(cl), _ptr(cr), _ptr(he), float(cutoff),
+                                        _ptr(status), _ptr(obj), _ptr(x), _ptr(vout), _ptr(iters), _ptr(npiv),
+                                        _ptr(dvar), _ptr(ddir), _ptr(dval))
         self.ctx.check(rc, 'mipx_lp_plunge_batch')
         return dict(status=status, obj=obj, x=x, vstat=vout, iters=iters, npivots=npiv, dive_var=dvar,
                     dive_dir=ddir, dive_val=dval)
@@ -643,9 +632,6 @@ class Tree:
         rule = {'most fractional': 0, 'pseudo cost': 1}[branch_rule]
         search = {'best first': 0, 'depth first': 1}[search_rule]
         h = _vp()
-        L = lib()
-        L.mipx_tree_create_ex.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_int64, C.POINTER(CutParams), C.POINTER(_vp)]
         cp = None
         if cut_params is not None:
             cp = CutParams(max_cut_generation_iterations=10, max_nonzero_coefs=1000000, max_cuts_per_node=0,
@@ -655,9 +641,9 @@ class Tree:
             for key, value in cut_params.items():
                 assert hasattr(cp, key), f'unknown cut parameter {key}'
                 setattr(cp, key, value)
-        rc = L.mipx_tree_create_ex(problem._h, _ptr(ints), len(ints), _ptr(l), _ptr(u), rule,
-                                   search, int(strong_branch_iters), int(max_batch),
-                                   int(pool_capacity), None if cp is None else C.byref(cp), C.byref(h))
+        rc = lib().mipx_tree_create_ex(problem._h, _ptr(ints), len(ints), _ptr(l), _ptr(u), rule,
+                                       search, int(strong_branch_iters), int(max_batch),
+                                       int(pool_capacity), None if cp is None else C.byref(cp), C.byref(h))
         problem.ctx.check(rc, 'mipx_tree_create_ex')
         self.cuts = cp is not None
         self._h = h
@@ -680,17 +666,12 @@ class Tree:
 
     def reanchor(self, max_nodes):
         """Give the first max_nodes open nodes an anchor of their own (mipx_tree_reanchor)."""
-        L = lib()
-        L.mipx_tree_reanchor.argtypes = [_vp, C.c_int64]
-        self.problem.ctx.check(L.mipx_tree_reanchor(self._h, int(max_nodes)), 'mipx_tree_reanchor')
+        self.problem.ctx.check(lib().mipx_tree_reanchor(self._h, int(max_nodes)), 'mipx_tree_reanchor')
 
     def peek_anchors(self, max_nodes):
         """Anchor-table entry of each open node, in the order of peek_open (-1: the root's anchor)."""
         a = np.full(int(max_nodes), -1, np.int32)
-        L = lib()
-        L.mipx_tree_peek_anchors.argtypes = [_vp, C.c_int64, _vp]
-        L.mipx_tree_peek_anchors.restype = C.c_int64
-        k = L.mipx_tree_peek_anchors(self._h, int(max_nodes), _ptr(a))
+        k = lib().mipx_tree_peek_anchors(self._h, int(max_nodes), _ptr(a))
         if k < 0:
             self.problem.ctx.check(int(k), 'mipx_tree_peek_anchors')
         return a[:k]
@@ -698,8 +679,6 @@ class Tree:
     def anchor_table(self):
         """(T, vec, idx) of the re-anchoring table as host arrays, or None."""
         L = lib()
-        L.mipx_tree_anchor_table.argtypes = [_vp, _vp, _vp, _vp]
-        L.mipx_tree_anchor_table.restype = C.c_int64
         K = L.mipx_tree_anchor_table(self._h, None, None, None)
         if K <= 0:
             return None
@@ -720,12 +699,9 @@ class Tree:
         steps already queued (mipx_tree_set_step_hook): the place for a rank's all-reduce.  fn may
         use stats(), pseudo_cost_arrays(), set_primal_bound(), set_pseudo_cost_arrays(); a truthy
         return value or an exception stops the solve.  fn=None removes the hook."""
-        L = lib()
-        proto = C.CFUNCTYPE(C.c_int, _vp)
-        L.mipx_tree_set_step_hook.argtypes = [_vp, proto, _vp, C.c_int]
         if fn is None:
             self._hook = None
-            rc = L.mipx_tree_set_step_hook(self._h, proto(), None, 0)
+            rc = lib().mipx_tree_set_step_hook(self._h, TREE_HOOK(), None, 0)
         else:
             def trampoline(_user):
                 try:
@@ -733,25 +709,20 @@ class Tree:
                 except BaseException as e:  # never unwind through the C frames
                     self._hook_error = e
                     return 1
-            self._hook = proto(trampoline)  # keep the thunk alive as long as it is installed
-            rc = L.mipx_tree_set_step_hook(self._h, self._hook, None, int(every_steps))
+            self._hook = TREE_HOOK(trampoline)  # keep the thunk alive as long as it is installed
+            rc = lib().mipx_tree_set_step_hook(self._h, self._hook, None, int(every_steps))
         self.problem.ctx.check(rc, 'mipx_tree_set_step_hook')
 
     def set_comm(self, comm, every_steps=5):
         """Attach the communicator: solve() becomes a collective call (mipx_tree_set_comm)."""
-        L = lib()
-        L.mipx_tree_set_comm.argtypes = [_vp, _vp, C.c_int]
         self._comm = comm
-        self.problem.ctx.check(L.mipx_tree_set_comm(self._h, None if comm is None else comm._h, int(every_steps)),
+        self.problem.ctx.check(lib().mipx_tree_set_comm(self._h, None if comm is None else comm._h, int(every_steps)),
                                'mipx_tree_set_comm')
 
     def migrate_self(self, amount):
         """Test hook (mipx_tree_migrate_self): up to `amount` open nodes leave and re-enter this rank through
         the communicator's point-to-point path; returns how many moved."""
-        L = lib()
-        L.mipx_tree_migrate_self.argtypes = [_vp, C.c_int64]
-        L.mipx_tree_migrate_self.restype = C.c_int64
-        k = L.mipx_tree_migrate_self(self._h, int(amount))
+        k = lib().mipx_tree_migrate_self(self._h, int(amount))
         if k < 0:
             self.problem.ctx.check(int(k), 'mipx_tree_migrate_self')
         return int(k)
@@ -759,32 +730,24 @@ class Tree:
     def exchange_record(self):
         """The record this rank would post right now (mipx_tree_exchange_record; needs set_comm)."""
         r = np.zeros(exchange_record_len(self.problem.n))
-        L = lib()
-        L.mipx_tree_exchange_record.argtypes = [_vp, _vp]
-        self.problem.ctx.check(L.mipx_tree_exchange_record(self._h, _ptr(r)), 'mipx_tree_exchange_record')
+        self.problem.ctx.check(lib().mipx_tree_exchange_record(self._h, _ptr(r)), 'mipx_tree_exchange_record')
         return r
 
     def global_stats(self):
         st = GlobalStats()
-        L = lib()
-        L.mipx_tree_global_stats.argtypes = [_vp, C.POINTER(GlobalStats)]
-        self.problem.ctx.check(L.mipx_tree_global_stats(self._h, C.byref(st)), 'mipx_tree_global_stats')
+        self.problem.ctx.check(lib().mipx_tree_global_stats(self._h, C.byref(st)), 'mipx_tree_global_stats')
         return {k: getattr(st, k) for k, _ in st._fields_}
 
     def kernel_ms(self):
         """Device time by kernel (ms): dict(node_lp, gomory, select) (mipx_tree_kernel_ms)."""
         out = (C.c_double * 4)()
-        L = lib()
-        L.mipx_tree_kernel_ms.argtypes = [_vp, _vp]
-        self.problem.ctx.check(L.mipx_tree_kernel_ms(self._h, out), 'mipx_tree_kernel_ms')
+        self.problem.ctx.check(lib().mipx_tree_kernel_ms(self._h, out), 'mipx_tree_kernel_ms')
         return dict(node_lp=out[0], gomory=out[1], select=out[2])
 
     def cut_stats(self):
         """The running GMIC totals of BaseNode._base_bound over every evaluated node (+ 'dropped')."""
         out = (C.c_int64 * 8)()
-        L = lib()
-        L.mipx_tree_cut_stats.argtypes = [_vp, _vp]
-        self.problem.ctx.check(L.mipx_tree_cut_stats(self._h, out), 'mipx_tree_cut_stats')
+        self.problem.ctx.check(lib().mipx_tree_cut_stats(self._h, out), 'mipx_tree_cut_stats')
         d = {k: int(out[i]) for i, k in enumerate(CUT_TOTAL_KEYS)}
         d['dropped'] = int(out[7])
         return d
@@ -829,9 +792,7 @@ class Tree:
     def set_pseudo_cost_arrays(self, cl, cr, tl, tr):
         cl = np.ascontiguousarray(cl, np.float64); cr = np.ascontiguousarray(cr, np.float64)
         tl = np.ascontiguousarray(tl, np.int32); tr = np.ascontiguousarray(tr, np.int32)
-        L = lib()
-        L.mipx_tree_set_pseudo_costs.argtypes = [_vp, _vp, _vp, _vp, _vp]
-        self.problem.ctx.check(L.mipx_tree_set_pseudo_costs(self._h, _ptr(cl), _ptr(cr), _ptr(tl), _ptr(tr)),
+        self.problem.ctx.check(lib().mipx_tree_set_pseudo_costs(self._h, _ptr(cl), _ptr(cr), _ptr(tl), _ptr(tr)),
                                'mipx_tree_set_pseudo_costs')
 
     def peek_open(self, max_nodes):
@@ -866,8 +827,6 @@ class Tree:
         """(nodes, 8) per evaluated node in trace order: cut rounds, iterations / number of GMICs created,
         added, removed, cut rows at the end (mipx_tree_trace_cuts)."""
         L = lib()
-        L.mipx_tree_trace_cuts.argtypes = [_vp, C.c_int64, _vp]
-        L.mipx_tree_trace_cuts.restype = C.c_int64
         k = L.mipx_tree_trace_cuts(self._h, 0, None)
         out = np.zeros((max(k, 0), 8), np.int32)
         L.mipx_tree_trace_cuts(self._h, k, _ptr(out))
@@ -877,9 +836,6 @@ class Tree:
         """(node ids, cut counts, cut lists, basis codes of the cut rows) of the open nodes, in the order
         of peek_open (mipx_tree_peek_cuts)."""
         L = lib()
-        L.mipx_tree_peek_cuts.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp]
-        L.mipx_tree_peek_cuts.restype = C.c_int64
-        L.mipx_tree_cut_rows_per_node.argtypes = [_vp]
         kc = max(0, L.mipx_tree_cut_rows_per_node(self._h))
         ids = np.zeros(max_nodes, np.int64); ncut = np.zeros(max_nodes, np.int32)
         lists = np.zeros((max_nodes, max(kc, 1)), np.int32); codes = np.zeros((max_nodes, max(kc, 1)), np.int8)
@@ -891,8 +847,6 @@ class Tree:
     def cut_store(self):
         """(pi, pi0) of every cut added so far (mipx_tree_cut_store)."""
         L = lib()
-        L.mipx_tree_cut_store.argtypes = [_vp, C.c_int64, _vp, _vp]
-        L.mipx_tree_cut_store.restype = C.c_int64
         k = L.mipx_tree_cut_store(self._h, 0, None, None)
         if k < 0:
             self.problem.ctx.check(int(k), 'mipx_tree_cut_store')
@@ -935,8 +889,6 @@ def default_context():
 def debug_dump(problem, l, u, vstat=None, max_iter=0):
     """Test hook: solve one LP and return the kernel's final tableau state (see mipx.h)."""
     L = lib()
-    L.mipx_debug_enable.argtypes = [_vp]
-    L.mipx_debug_read.argtypes = [_vp, _vp, _vp, _vp]
     problem.ctx.check(L.mipx_debug_enable(problem._h), 'mipx_debug_enable')
     res = problem.solve_batch(np.asarray(l, float)[None], np.asarray(u, float)[None],
                               None if vstat is None else np.asarray(vstat, np.int8)[None], max_iter)

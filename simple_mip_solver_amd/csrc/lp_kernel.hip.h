@@ -39,17 +39,17 @@ constexpr double kBTol = 1e-9;
 constexpr double kMReport = 1e10;  // stands for the symbolic bound M when reporting an unbounded x
 
 struct LpArgs {
-    int m, n;
-    const double *A, *b, *c;       // shared by the batch (strides 0) or one problem per node
-    size_t A_stride, b_stride, c_stride;  // elements between consecutive nodes' A / b / c
-    const double *l, *u;           // batch x n
-    const int8_t *vstat_in;        // batch x (n+m) or nullptr
-    const int32_t *slot;           // optional: node k reads l/u/vstat_in at row slot[k] (node pool)
+    int m = 0, n = 0;
+    const double *A = nullptr, *b = nullptr, *c = nullptr;  // shared by the batch (strides 0) or one problem per node
+    size_t A_stride = 0, b_stride = 0, c_stride = 0;  // elements between consecutive nodes' A / b / c
+    const double *l = nullptr, *u = nullptr;  // batch x n
+    const int8_t *vstat_in = nullptr;  // batch x (n+m) or nullptr
+    const int32_t *slot = nullptr;  // optional: node k reads l/u/vstat_in at row slot[k] (node pool)
     // optional anchor: tableau state of some basis of the same rows (layout of the dump: T m x n,
     // vec = [d (n) | beta0 (m) | ..], idx = [nvar (n) | bvar (m) | ..]); warm starts refactor from it
     // instead of from the slack basis (fewer pivots when the bases are close, e.g. the root's)
-    const double *anchor_T, *anchor_vec;
-    const int32_t *anchor_idx;
+    const double *anchor_T = nullptr, *anchor_vec = nullptr;
+    const int32_t *anchor_idx = nullptr;
     // optional table of anchors (frontier engine): node k of the batch starts from entry
     // anchor_sel[k] of the table (same layout per entry, entries m*n / n+3m / 2n+m apart), or from
     // the single anchor above where the entry is -1.  Indexed by batch position like `slot`, so that
@@ -57,21 +57,21 @@ struct LpArgs {
     const int32_t *anchor_sel = nullptr;
     const double *atab_T = nullptr, *atab_vec = nullptr;
     const int32_t *atab_idx = nullptr;
-    int refactor_only;             // stop after the refactorisation (used to build an anchor)
-    int max_iter;
-    int32_t *status;
-    double *obj;
-    double *x;                     // batch x n
-    double *y;                     // batch x m
-    int8_t *vstat_out;             // batch x (n+m)
-    int32_t *iters;
-    int32_t *npivots;
-    int batch;
+    int refactor_only = 0;         // stop after the refactorisation (used to build an anchor)
+    int max_iter = 0;
+    int32_t *status = nullptr;
+    double *obj = nullptr;
+    double *x = nullptr;           // batch x n
+    double *y = nullptr;           // batch x m
+    int8_t *vstat_out = nullptr;   // batch x (n+m)
+    int32_t *iters = nullptr;
+    int32_t *npivots = nullptr;
+    int batch = 0;
     // optional debug dump of the final tableau state of node 0 (nullptr in production)
-    double *dbg_T;      // m x n row-major
-    double *dbg_vec;    // [d (n) | beta0 (m) | ba (m) | bb (m)]
-    int32_t *dbg_idx;   // [nvar (n) | bvar (m) | side (n)]
-    int dbg_all;        // 0: node 0 only; 1: every node k at offsets k*m*n, k*(n+3m), k*(2n+m)
+    double *dbg_T = nullptr;      // m x n row-major
+    double *dbg_vec = nullptr;    // [d (n) | beta0 (m) | ba (m) | bb (m)]
+    int32_t *dbg_idx = nullptr;   // [nvar (n) | bvar (m) | side (n)]
+    int dbg_all = 0;              // 0: node 0 only; 1: every node k at offsets k*m*n, k*(n+3m), k*(2n+m)
     unsigned long long *prof = nullptr;  // MIPX_KPROF builds only: per-section cycle totals of one wave
     int prof_wave = 0;
     // optional dive (frontier engine): when the node LP ends optimal, fractional and below the
@@ -106,6 +106,8 @@ struct LpArgs {
     const int32_t *active = nullptr;  // optional: node k is skipped (nothing read or written) where active[k] == 0
     int cold = 0;                     // the caller vouches that vstat_in holds no basis (all codes 0) and the nodes no cut row: a cold start (K1c may take it)
 };
+// (every field has a default, so a launch site sets only what differs; passed by value as a kernel argument)
+static_assert(std::is_trivially_copyable<LpArgs>::value, "LpArgs is a kernel argument");
 
 constexpr double kVarEps = 1e-4;  // utils/tolerance.py:2 variable_epsilon
 constexpr int kDseRefresh = 64;   // iterations after which the steepest-edge weights are recomputed from the tableau

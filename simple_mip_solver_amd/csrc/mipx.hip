@@ -266,6 +266,70 @@ int launch_lp_any(mipx_problem *p, mipx::LpArgs &a, int batch, hipStream_t strea
     return MIPX_OK;
 }
 
+// What every launch on a problem's rows shares: its (m, n, A, b, c), and its anchor where one is set
+// and the caller takes it.
+mipx::LpArgs problem_args(const mipx_problem *p, bool anchor = true) {
+    mipx::LpArgs a;
+    a.m = p->m; a.n = p->n;
+    a.A = p->dA; a.b = p->db; a.c = p->dc;
+    if (anchor && p->anchor_on) { a.anchor_T = p->anchor_T; a.anchor_vec = p->anchor_vec; a.anchor_idx = p->anchor_idx; }
+    return a;
+}
+
+// Device staging of a host-buffer entry point: in() / out() / carve() lay out 256-byte-aligned slots of one
+// block; alloc() takes the block (a scratch buffer grown on demand, or one for this call only); upload()
+// queues the H2D copies; finish(rc) queues the D2H copies if rc is MIPX_OK, then always syncs the stream
+// (no copy into the caller's arrays is left pending), frees a one-call block and returns the first error.
+// Null host pointers are not copied.
+struct Staging {
+    struct Copy { void *host; size_t o, bytes; };
+    mipx_ctx *ctx;
+    const char *who;
+    size_t off = 0;
+    char *base = nullptr;
+    bool own = false;
+    std::vector<Copy> ups, downs;
+
+    Staging(mipx_ctx *c, const char *name) : ctx(c), who(name) {}
+    int err(const char *what, hipError_t e) { return fail(ctx, MIPX_EHIP, (std::string(who) + ": " + what).c_str(), e); }
+    size_t carve(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
+    void up(size_t o, const void *src, size_t bytes) { if (src) ups.push_back({(void *)src, o, bytes}); }
+    void down(void *dst, size_t o, size_t bytes) { if (dst) downs.push_back({dst, o, bytes}); }
+    size_t in(const void *src, size_t bytes) { const size_t o = carve(bytes); up(o, src, bytes); return o; }
+    size_t out(void *dst, size_t bytes) { const size_t o = carve(bytes); down(dst, o, bytes); return o; }
+    template <class T> T *at(size_t o) const { return (T *)(base + o); }
+    int alloc(void *&block, size_t &have) {
+        if (off > have) {
+            if (block) (void)hipFree(block);
+            block = nullptr;
+            have = 0;
+            if (hipError_t e = hipMalloc(&block, off)) return err("hipMalloc", e);
+            have = off;
+        }
+        base = (char *)block;
+        return MIPX_OK;
+    }
+    int alloc() {
+        if (hipError_t e = hipMalloc((void **)&base, off)) return err("hipMalloc", e);
+        own = true;
+        return MIPX_OK;
+    }
+    int upload() {
+        for (const Copy &c : ups)
+            if (hipError_t e = hipMemcpyAsync(base + c.o, c.host, c.bytes, hipMemcpyHostToDevice, ctx->stream)) return err("upload", e);
+        return MIPX_OK;
+    }
+    int finish(int rc) {
+        for (size_t k = 0; rc == MIPX_OK && k < downs.size(); k++)
+            if (hipError_t e = hipMemcpyAsync(downs[k].host, base + downs[k].o, downs[k].bytes, hipMemcpyDeviceToHost, ctx->stream))
+                rc = err("download", e);
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess && rc == MIPX_OK) rc = err("sync", e);
+        if (own) (void)hipFree(base);
+        return rc;
+    }
+};
+
 }  // namespace
 
 #include "cut_kernels.hip.h"
@@ -380,18 +444,11 @@ int mipx_lp_solve_batch_dev(mipx_problem *p, int batch, const double *l, const d
     if (batch < 0 || (batch > 0 && (!l || !u))) return fail(ctx, MIPX_EINVAL, "mipx_lp_solve_batch_dev: bad argument");
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    mipx::LpArgs a;
-    a.m = p->m; a.n = p->n;
-    a.A = p->dA; a.b = p->db; a.c = p->dc;
-    a.A_stride = a.b_stride = a.c_stride = 0;
-    a.l = l; a.u = u; a.vstat_in = vstat_in; a.slot = nullptr; a.max_iter = max_iter;
-    a.anchor_T = p->anchor_on ? p->anchor_T : nullptr;
-    a.anchor_vec = p->anchor_on ? p->anchor_vec : nullptr;
-    a.anchor_idx = p->anchor_on ? p->anchor_idx : nullptr;
-    a.refactor_only = 0;
+    mipx::LpArgs a = problem_args(p);
+    a.l = l; a.u = u; a.vstat_in = vstat_in; a.max_iter = max_iter;
     a.status = status; a.obj = obj; a.x = x; a.y = y; a.vstat_out = vstat_out;
     a.iters = iters; a.npivots = npivots; a.batch = batch;
-    a.dbg_T = p->dbg_T; a.dbg_vec = p->dbg_vec; a.dbg_idx = p->dbg_idx; a.dbg_all = 0;
+    a.dbg_T = p->dbg_T; a.dbg_vec = p->dbg_vec; a.dbg_idx = p->dbg_idx;
     return launch_lp_any(p, a, batch);
 }
 
@@ -405,40 +462,20 @@ int mipx_lp_solve_batch(mipx_problem *p, int batch, const double *l, const doubl
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, n = (size_t)p->n, m = (size_t)p->m, nv = n + m;
-    // carve one staging allocation
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_l = carve(B * n * 8), o_u = carve(B * n * 8), o_vin = carve(B * nv),
-                 o_st = carve(B * 4), o_obj = carve(B * 8), o_x = carve(B * n * 8),
-                 o_y = carve(B * (m ? m : 1) * 8), o_vout = carve(B * nv), o_it = carve(B * 4),
-                 o_np = carve(B * 4);
-    if (off > p->scratch_bytes) {
-        if (p->scratch) (void)hipFree(p->scratch);
-        p->scratch = nullptr;
-        p->scratch_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&p->scratch, off));
-        p->scratch_bytes = off;
-    }
-    char *base = (char *)p->scratch;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_l, l, B * n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_u, u, B * n * 8, hipMemcpyHostToDevice, st));
-    if (vstat_in) HIP_TRY(ctx, hipMemcpyAsync(base + o_vin, vstat_in, B * nv, hipMemcpyHostToDevice, st));
-    int rc = mipx_lp_solve_batch_dev(
-        p, batch, (const double *)(base + o_l), (const double *)(base + o_u),
-        vstat_in ? (const int8_t *)(base + o_vin) : nullptr, max_iter, (int32_t *)(base + o_st),
-        (double *)(base + o_obj), (double *)(base + o_x), (double *)(base + o_y),
-        (int8_t *)(base + o_vout), (int32_t *)(base + o_it), (int32_t *)(base + o_np));
-    if (rc) return rc;
-    if (status) HIP_TRY(ctx, hipMemcpyAsync(status, base + o_st, B * 4, hipMemcpyDeviceToHost, st));
-    if (obj) HIP_TRY(ctx, hipMemcpyAsync(obj, base + o_obj, B * 8, hipMemcpyDeviceToHost, st));
-    if (x) HIP_TRY(ctx, hipMemcpyAsync(x, base + o_x, B * n * 8, hipMemcpyDeviceToHost, st));
-    if (y && m) HIP_TRY(ctx, hipMemcpyAsync(y, base + o_y, B * m * 8, hipMemcpyDeviceToHost, st));
-    if (vstat_out) HIP_TRY(ctx, hipMemcpyAsync(vstat_out, base + o_vout, B * nv, hipMemcpyDeviceToHost, st));
-    if (iters) HIP_TRY(ctx, hipMemcpyAsync(iters, base + o_it, B * 4, hipMemcpyDeviceToHost, st));
-    if (npivots) HIP_TRY(ctx, hipMemcpyAsync(npivots, base + o_np, B * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return MIPX_OK;
+    Staging S(ctx, "mipx_lp_solve_batch");
+    const size_t o_l = S.in(l, B * n * 8), o_u = S.in(u, B * n * 8), o_vin = S.in(vstat_in, B * nv),
+                 o_st = S.out(status, B * 4), o_obj = S.out(obj, B * 8), o_x = S.out(x, B * n * 8),
+                 o_y = S.carve(B * (m ? m : 1) * 8);
+    S.down(m ? y : nullptr, o_y, B * m * 8);
+    const size_t o_vout = S.out(vstat_out, B * nv), o_it = S.out(iters, B * 4), o_np = S.out(npivots, B * 4);
+    int rc = S.alloc(p->scratch, p->scratch_bytes);
+    if (rc == MIPX_OK) rc = S.upload();
+    if (rc == MIPX_OK)
+        rc = mipx_lp_solve_batch_dev(p, batch, S.at<const double>(o_l), S.at<const double>(o_u),
+                                     vstat_in ? S.at<const int8_t>(o_vin) : nullptr, max_iter, S.at<int32_t>(o_st),
+                                     S.at<double>(o_obj), S.at<double>(o_x), S.at<double>(o_y),
+                                     S.at<int8_t>(o_vout), S.at<int32_t>(o_it), S.at<int32_t>(o_np));
+    return S.finish(rc);
 }
 
 int mipx_lp_solve_batch_cuts(mipx_problem *p, int batch, const double *l, const double *u,
@@ -467,56 +504,30 @@ int mipx_lp_solve_batch_cuts(mipx_problem *p, int batch, const double *l, const 
         return fail(ctx, MIPX_ETOOBIG, "mipx_lp_solve_batch_cuts: m + cuts exceeds the LP kernels of this shape");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, n = (size_t)p->n, M = (size_t)p->m + kc, nvs = n + M, NC = (size_t)(ncuts_total ? ncuts_total : 1);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_l = carve(B * n * 8), o_u = carve(B * n * 8), o_vin = carve(B * nvs), o_cp = carve(NC * n * 8),
-                 o_c0 = carve(NC * 8), o_nc = carve(B * 4), o_id = carve(B * kc * 4), o_st = carve(B * 4),
-                 o_obj = carve(B * 8), o_x = carve(B * n * 8), o_y = carve(B * M * 8), o_vout = carve(B * nvs),
-                 o_it = carve(B * 4), o_np = carve(B * 4);
-    char *base = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&base, off));
-    hipStream_t st = ctx->stream;
-    auto run = [&]() -> int {
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_l, l, B * n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_u, u, B * n * 8, hipMemcpyHostToDevice, st));
-        if (vstat_in) HIP_TRY(ctx, hipMemcpyAsync(base + o_vin, vstat_in, B * nvs, hipMemcpyHostToDevice, st));
-        if (ncuts_total) {
-            HIP_TRY(ctx, hipMemcpyAsync(base + o_cp, cut_pi, (size_t)ncuts_total * n * 8, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(base + o_c0, cut_pi0, (size_t)ncuts_total * 8, hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_nc, ncut, B * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_id, cut_ids, B * kc * 4, hipMemcpyHostToDevice, st));
-        mipx::LpArgs a;
-        a.m = p->m; a.n = p->n;
-        a.A = p->dA; a.b = p->db; a.c = p->dc;
-        a.A_stride = a.b_stride = a.c_stride = 0;
-        a.l = (const double *)(base + o_l); a.u = (const double *)(base + o_u);
-        a.vstat_in = vstat_in ? (const int8_t *)(base + o_vin) : nullptr;
-        a.slot = nullptr; a.max_iter = max_iter;
-        a.anchor_T = nullptr; a.anchor_vec = nullptr; a.anchor_idx = nullptr; a.refactor_only = 0;
-        a.status = (int32_t *)(base + o_st); a.obj = (double *)(base + o_obj); a.x = (double *)(base + o_x);
-        a.y = (double *)(base + o_y); a.vstat_out = (int8_t *)(base + o_vout);
-        a.iters = (int32_t *)(base + o_it); a.npivots = (int32_t *)(base + o_np); a.batch = batch;
-        a.dbg_T = nullptr; a.dbg_vec = nullptr; a.dbg_idx = nullptr; a.dbg_all = 0;
-        a.ncut = (const int32_t *)(base + o_nc); a.cut_ids = (const int32_t *)(base + o_id);
-        a.cut_pi = (const double *)(base + o_cp); a.cut_pi0 = (const double *)(base + o_c0);
-        a.cut_stride = kc; a.mstride = (int)M; a.vstat_by_node = 0; a.active = nullptr;
-        const int rc = launch_lp_any(p, a, batch, nullptr, p->m + maxc);
-        if (rc) return rc;
-        if (status) HIP_TRY(ctx, hipMemcpyAsync(status, base + o_st, B * 4, hipMemcpyDeviceToHost, st));
-        if (obj) HIP_TRY(ctx, hipMemcpyAsync(obj, base + o_obj, B * 8, hipMemcpyDeviceToHost, st));
-        if (x) HIP_TRY(ctx, hipMemcpyAsync(x, base + o_x, B * n * 8, hipMemcpyDeviceToHost, st));
-        if (y) HIP_TRY(ctx, hipMemcpyAsync(y, base + o_y, B * M * 8, hipMemcpyDeviceToHost, st));
-        if (vstat_out) HIP_TRY(ctx, hipMemcpyAsync(vstat_out, base + o_vout, B * nvs, hipMemcpyDeviceToHost, st));
-        if (iters) HIP_TRY(ctx, hipMemcpyAsync(iters, base + o_it, B * 4, hipMemcpyDeviceToHost, st));
-        if (npivots) HIP_TRY(ctx, hipMemcpyAsync(npivots, base + o_np, B * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        return MIPX_OK;
-    };
-    const int rc = run();
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(base);
-    return rc;
+    Staging S(ctx, "mipx_lp_solve_batch_cuts");
+    const size_t o_l = S.in(l, B * n * 8), o_u = S.in(u, B * n * 8), o_vin = S.in(vstat_in, B * nvs),
+                 o_cp = S.carve(NC * n * 8), o_c0 = S.carve(NC * 8);
+    S.up(o_cp, ncuts_total ? cut_pi : nullptr, (size_t)ncuts_total * n * 8);
+    S.up(o_c0, ncuts_total ? cut_pi0 : nullptr, (size_t)ncuts_total * 8);
+    const size_t o_nc = S.in(ncut, B * 4), o_id = S.in(cut_ids, B * kc * 4), o_st = S.out(status, B * 4),
+                 o_obj = S.out(obj, B * 8), o_x = S.out(x, B * n * 8), o_y = S.out(y, B * M * 8),
+                 o_vout = S.out(vstat_out, B * nvs), o_it = S.out(iters, B * 4), o_np = S.out(npivots, B * 4);
+    int rc = S.alloc();
+    if (rc == MIPX_OK) rc = S.upload();
+    if (rc == MIPX_OK) {
+        mipx::LpArgs a = problem_args(p, false);
+        a.l = S.at<const double>(o_l); a.u = S.at<const double>(o_u);
+        a.vstat_in = vstat_in ? S.at<const int8_t>(o_vin) : nullptr;
+        a.max_iter = max_iter;
+        a.status = S.at<int32_t>(o_st); a.obj = S.at<double>(o_obj); a.x = S.at<double>(o_x);
+        a.y = S.at<double>(o_y); a.vstat_out = S.at<int8_t>(o_vout);
+        a.iters = S.at<int32_t>(o_it); a.npivots = S.at<int32_t>(o_np); a.batch = batch;
+        a.ncut = S.at<const int32_t>(o_nc); a.cut_ids = S.at<const int32_t>(o_id);
+        a.cut_pi = S.at<const double>(o_cp); a.cut_pi0 = S.at<const double>(o_c0);
+        a.cut_stride = kc; a.mstride = (int)M;
+        rc = launch_lp_any(p, a, batch, nullptr, p->m + maxc);
+    }
+    return S.finish(rc);
 }
 
 int mipx_lp_dive_batch(mipx_problem *p, int batch, const double *l, const double *u,
@@ -546,67 +557,40 @@ int mipx_lp_plunge_batch(mipx_problem *p, int batch, int depth, const double *l,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, n = (size_t)p->n, m = (size_t)p->m, nv = n + m, ni = (size_t)(n_int ? n_int : 1);
     const size_t LB = ((size_t)depth + 1) * B, DB = (size_t)depth * B;   // output rows, decisions
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_l = carve(B * n * 8), o_u = carve(B * n * 8), o_vin = carve(B * nv),
-                 o_st = carve(LB * 4), o_obj = carve(LB * 8), o_x = carve(LB * n * 8),
-                 o_vout = carve(LB * nv), o_it = carve(LB * 4), o_np = carve(LB * 4),
-                 o_dv = carve(DB * 4), o_dd = carve(DB * 4), o_dx = carve(DB * 8), o_ii = carve(ni * 4),
-                 o_cl = carve(n * 8), o_cr = carve(n * 8), o_he = carve(n);
-    char *base = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&base, off));
+    Staging S(ctx, "mipx_lp_plunge_batch");
+    const size_t o_l = S.in(l, B * n * 8), o_u = S.in(u, B * n * 8), o_vin = S.in(vstat_in, B * nv),
+                 o_st = S.out(status, LB * 4), o_obj = S.out(obj, LB * 8), o_x = S.out(x, LB * n * 8),
+                 o_vout = S.out(vstat_out, LB * nv), o_it = S.out(iters, LB * 4), o_np = S.out(npivots, LB * 4),
+                 o_dv = S.out(dive_var, DB * 4), o_dd = S.out(dive_dir, DB * 4), o_dx = S.out(dive_val, DB * 8),
+                 o_ii = S.carve(ni * 4);
+    S.up(o_ii, n_int ? int_idx : nullptr, (size_t)n_int * 4);
+    const size_t o_cl = S.in(cost_l, n * 8), o_cr = S.in(cost_r, n * 8), o_he = S.in(has_entry, n);
     hipStream_t st = ctx->stream;
-    auto run = [&]() -> int {
-        HIP_TRY(ctx, hipMemsetAsync(base, 0, off, st));
-        HIP_TRY(ctx, hipMemsetAsync(base + o_st + B * 4, 0xff, DB * 4, st));  // no child: status -1
-        HIP_TRY(ctx, hipMemsetAsync(base + o_dv, 0xff, DB * 4, st));          // no dive: -1
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_l, l, B * n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_u, u, B * n * 8, hipMemcpyHostToDevice, st));
-        if (vstat_in) HIP_TRY(ctx, hipMemcpyAsync(base + o_vin, vstat_in, B * nv, hipMemcpyHostToDevice, st));
-        if (n_int) HIP_TRY(ctx, hipMemcpyAsync(base + o_ii, int_idx, (size_t)n_int * 4, hipMemcpyHostToDevice, st));
-        if (cost_l) HIP_TRY(ctx, hipMemcpyAsync(base + o_cl, cost_l, n * 8, hipMemcpyHostToDevice, st));
-        if (cost_r) HIP_TRY(ctx, hipMemcpyAsync(base + o_cr, cost_r, n * 8, hipMemcpyHostToDevice, st));
-        if (has_entry) HIP_TRY(ctx, hipMemcpyAsync(base + o_he, has_entry, n, hipMemcpyHostToDevice, st));
-        mipx::LpArgs a;
-        a.m = p->m; a.n = p->n;
-        a.A = p->dA; a.b = p->db; a.c = p->dc;
-        a.A_stride = a.b_stride = a.c_stride = 0;
-        a.l = (const double *)(base + o_l); a.u = (const double *)(base + o_u);
-        a.vstat_in = vstat_in ? (const int8_t *)(base + o_vin) : nullptr;
-        a.slot = nullptr; a.max_iter = max_iter;
-        a.anchor_T = p->anchor_on ? p->anchor_T : nullptr;
-        a.anchor_vec = p->anchor_on ? p->anchor_vec : nullptr;
-        a.anchor_idx = p->anchor_on ? p->anchor_idx : nullptr;
-        a.refactor_only = 0;
-        a.status = (int32_t *)(base + o_st); a.obj = (double *)(base + o_obj); a.x = (double *)(base + o_x);
-        a.y = nullptr; a.vstat_out = (int8_t *)(base + o_vout);
-        a.iters = (int32_t *)(base + o_it); a.npivots = (int32_t *)(base + o_np); a.batch = batch;
-        a.dbg_T = nullptr; a.dbg_vec = nullptr; a.dbg_idx = nullptr; a.dbg_all = 0;
+    int rc = S.alloc();
+    if (rc == MIPX_OK) {
+        hipError_t e = hipMemsetAsync(S.base, 0, S.off, st);
+        if (e == hipSuccess) e = hipMemsetAsync(S.base + o_st + B * 4, 0xff, DB * 4, st);  // no child: status -1
+        if (e == hipSuccess) e = hipMemsetAsync(S.base + o_dv, 0xff, DB * 4, st);          // no dive: -1
+        if (e != hipSuccess) rc = S.err("preset", e);
+    }
+    if (rc == MIPX_OK) rc = S.upload();
+    if (rc == MIPX_OK) {
+        mipx::LpArgs a = problem_args(p);
+        a.l = S.at<const double>(o_l); a.u = S.at<const double>(o_u);
+        a.vstat_in = vstat_in ? S.at<const int8_t>(o_vin) : nullptr;
+        a.max_iter = max_iter;
+        a.status = S.at<int32_t>(o_st); a.obj = S.at<double>(o_obj); a.x = S.at<double>(o_x);
+        a.vstat_out = S.at<int8_t>(o_vout);
+        a.iters = S.at<int32_t>(o_it); a.npivots = S.at<int32_t>(o_np); a.batch = batch;
         a.dive = depth; a.dive_off = batch; a.rule = rule; a.n_int = n_int;
-        a.int_idx = (const int32_t *)(base + o_ii);
-        a.cost_l = (const double *)(base + o_cl); a.cost_r = (const double *)(base + o_cr);
-        a.has_entry = (const uint8_t *)(base + o_he);
+        a.int_idx = S.at<const int32_t>(o_ii);
+        a.cost_l = S.at<const double>(o_cl); a.cost_r = S.at<const double>(o_cr);
+        a.has_entry = S.at<const uint8_t>(o_he);
         a.dive_cutoff = cutoff;
-        a.dive_var = (int32_t *)(base + o_dv); a.dive_dir = (int32_t *)(base + o_dd);
-        a.dive_val = (double *)(base + o_dx);
-        const int rc = launch_lp_any(p, a, batch);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(status, base + o_st, LB * 4, hipMemcpyDeviceToHost, st));
-        if (obj) HIP_TRY(ctx, hipMemcpyAsync(obj, base + o_obj, LB * 8, hipMemcpyDeviceToHost, st));
-        if (x) HIP_TRY(ctx, hipMemcpyAsync(x, base + o_x, LB * n * 8, hipMemcpyDeviceToHost, st));
-        if (vstat_out) HIP_TRY(ctx, hipMemcpyAsync(vstat_out, base + o_vout, LB * nv, hipMemcpyDeviceToHost, st));
-        if (iters) HIP_TRY(ctx, hipMemcpyAsync(iters, base + o_it, LB * 4, hipMemcpyDeviceToHost, st));
-        if (npivots) HIP_TRY(ctx, hipMemcpyAsync(npivots, base + o_np, LB * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(dive_var, base + o_dv, DB * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(dive_dir, base + o_dd, DB * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(dive_val, base + o_dx, DB * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        return MIPX_OK;
-    };
-    const int rc = run();
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(base);
-    return rc;
+        a.dive_var = S.at<int32_t>(o_dv); a.dive_dir = S.at<int32_t>(o_dd); a.dive_val = S.at<double>(o_dx);
+        rc = launch_lp_any(p, a, batch);
+    }
+    return S.finish(rc);
 }
 
 int mipx_problem_set_anchor(mipx_problem *p, const int8_t *vstat) {
@@ -626,15 +610,9 @@ int mipx_problem_set_anchor(mipx_problem *p, const int8_t *vstat) {
     HIP_TRY(ctx, hipMalloc((void **)&dv, nv));
     HIP_TRY(ctx, hipMemset(zeros, 0, n * 8));
     HIP_TRY(ctx, hipMemcpy(dv, vstat, nv, hipMemcpyHostToDevice));
-    mipx::LpArgs a;
-    a.m = p->m; a.n = p->n;
-    a.A = p->dA; a.b = p->db; a.c = p->dc;
-    a.A_stride = a.b_stride = a.c_stride = 0;
-    a.l = zeros; a.u = zeros; a.vstat_in = dv; a.slot = nullptr; a.max_iter = 0;
-    a.anchor_T = nullptr; a.anchor_vec = nullptr; a.anchor_idx = nullptr; a.refactor_only = 1;
-    a.status = nullptr; a.obj = nullptr; a.x = nullptr; a.y = nullptr; a.vstat_out = nullptr;
-    a.iters = nullptr; a.npivots = nullptr; a.batch = 1;
-    a.dbg_T = p->anchor_T; a.dbg_vec = p->anchor_vec; a.dbg_idx = p->anchor_idx; a.dbg_all = 0;
+    mipx::LpArgs a = problem_args(p, false);
+    a.l = zeros; a.u = zeros; a.vstat_in = dv; a.refactor_only = 1; a.batch = 1;
+    a.dbg_T = p->anchor_T; a.dbg_vec = p->anchor_vec; a.dbg_idx = p->anchor_idx;
     const int lrc = launch_lp_any(p, a, 1);
     hipError_t e = lrc == MIPX_OK ? hipStreamSynchronize(ctx->stream) : hipSuccess;
     (void)hipFree(zeros);
@@ -679,52 +657,35 @@ int mipx_lp_solve_multi(mipx_ctx *ctx, int m, int n, int batch, const double *A,
     if (!cfg) return fail(ctx, MIPX_ETOOBIG, "mipx_lp_solve_multi: (m,n) too big");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, nn = (size_t)n, mm = (size_t)(m ? m : 1), nv = (size_t)n + m;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_A = carve(B * mm * nn * 8), o_b = carve(B * mm * 8), o_c = carve(B * nn * 8),
-                 o_l = carve(B * nn * 8), o_u = carve(B * nn * 8), o_st = carve(B * 4),
-                 o_obj = carve(B * 8), o_x = carve(B * nn * 8), o_v = carve(B * nv),
-                 o_it = carve(B * 4), o_np = carve(B * 4);
-    char *base = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&base, off));
+    Staging S(ctx, "mipx_lp_solve_multi");
+    const size_t o_A = S.carve(B * mm * nn * 8), o_b = S.carve(B * mm * 8);
+    S.up(o_A, A, B * (size_t)m * nn * 8);
+    S.up(o_b, b, B * (size_t)m * 8);
+    const size_t o_c = S.in(c, B * nn * 8), o_l = S.in(l, B * nn * 8), o_u = S.in(u, B * nn * 8),
+                 o_st = S.out(status, B * 4), o_obj = S.out(obj, B * 8), o_x = S.out(x, B * nn * 8),
+                 o_v = S.out(vstat_out, B * nv), o_it = S.out(iters, B * 4), o_np = S.out(npivots, B * 4);
     hipStream_t st = ctx->stream;
-    int rc = MIPX_OK;
-    auto up = [&](size_t o, const void *src, size_t bytes) {
-        if (rc == MIPX_OK && hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-            rc = fail(ctx, MIPX_EHIP, "mipx_lp_solve_multi: upload");
-    };
-    up(o_A, A, B * (size_t)m * nn * 8); up(o_b, b, B * (size_t)m * 8); up(o_c, c, B * nn * 8);
-    up(o_l, l, B * nn * 8); up(o_u, u, B * nn * 8);
+    int rc = S.alloc();
+    if (rc == MIPX_OK) rc = S.upload();
+    if (rc == MIPX_OK && !ctx->k0 && (hipEventCreate(&ctx->k0) != hipSuccess || hipEventCreate(&ctx->k1) != hipSuccess))
+        rc = fail(ctx, MIPX_EHIP, "mipx_lp_solve_multi: events");
     if (rc == MIPX_OK) {
         mipx::LpArgs a;
         a.m = m; a.n = n;
-        a.A = (const double *)(base + o_A); a.b = (const double *)(base + o_b);
-        a.c = (const double *)(base + o_c);
+        a.A = S.at<const double>(o_A); a.b = S.at<const double>(o_b); a.c = S.at<const double>(o_c);
         a.A_stride = (size_t)m * nn; a.b_stride = (size_t)m; a.c_stride = nn;
-        a.l = (const double *)(base + o_l); a.u = (const double *)(base + o_u);
-        a.vstat_in = nullptr; a.slot = nullptr; a.max_iter = max_iter;
-    a.anchor_T = nullptr; a.anchor_vec = nullptr; a.anchor_idx = nullptr; a.refactor_only = 0;
-        a.status = (int32_t *)(base + o_st); a.obj = (double *)(base + o_obj);
-        a.x = (double *)(base + o_x); a.y = nullptr; a.vstat_out = (int8_t *)(base + o_v);
-        a.iters = (int32_t *)(base + o_it); a.npivots = (int32_t *)(base + o_np); a.batch = batch;
-        a.dbg_T = nullptr; a.dbg_vec = nullptr; a.dbg_idx = nullptr; a.dbg_all = 0;
-        if (!ctx->k0 && (hipEventCreate(&ctx->k0) != hipSuccess || hipEventCreate(&ctx->k1) != hipSuccess))
-            rc = fail(ctx, MIPX_EHIP, "mipx_lp_solve_multi: events");
-        if (rc == MIPX_OK) (void)hipEventRecord(ctx->k0, st);
+        a.l = S.at<const double>(o_l); a.u = S.at<const double>(o_u); a.max_iter = max_iter;
+        a.status = S.at<int32_t>(o_st); a.obj = S.at<double>(o_obj);
+        a.x = S.at<double>(o_x); a.vstat_out = S.at<int8_t>(o_v);
+        a.iters = S.at<int32_t>(o_it); a.npivots = S.at<int32_t>(o_np); a.batch = batch;
+        (void)hipEventRecord(ctx->k0, st);
         cfg->launch(a, batch, st);
         if (hipGetLastError() != hipSuccess) rc = fail(ctx, MIPX_EHIP, "mipx_lp_solve_multi: launch");
-        if (rc == MIPX_OK) (void)hipEventRecord(ctx->k1, st);
+        else (void)hipEventRecord(ctx->k1, st);
     }
-    auto down = [&](void *dst, size_t o, size_t bytes) {
-        if (dst && rc == MIPX_OK && hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
-            rc = fail(ctx, MIPX_EHIP, "mipx_lp_solve_multi: download");
-    };
-    down(status, o_st, B * 4); down(obj, o_obj, B * 8); down(x, o_x, B * nn * 8);
-    down(vstat_out, o_v, B * nv); down(iters, o_it, B * 4); down(npivots, o_np, B * 4);
-    if (hipStreamSynchronize(st) != hipSuccess && rc == MIPX_OK) rc = fail(ctx, MIPX_EHIP, "mipx_lp_solve_multi: sync");
+    rc = S.finish(rc);
     ctx->last_kernel_ms = -1.f;
     if (rc == MIPX_OK && hipEventElapsedTime(&ctx->last_kernel_ms, ctx->k0, ctx->k1) != hipSuccess) ctx->last_kernel_ms = -1.f;
-    (void)hipFree(base);
     return rc;
 }
 
@@ -739,54 +700,33 @@ int mipx_gomory_batch(mipx_problem *p, int batch, const double *l, const double 
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, n = (size_t)p->n, m = (size_t)(p->m ? p->m : 1), nv = n + p->m;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_l = carve(B * n * 8), o_u = carve(B * n * 8), o_v = carve(B * nv),
-                 o_x = carve(B * n * 8), o_int = carve(n), o_T = carve(B * m * n * 8),
-                 o_vec = carve(B * (n + 3 * m) * 8), o_idx = carve(B * (2 * n + m) * 4),
-                 o_nc = carve(B * 4), o_ri = carve(B * m * 4), o_pi = carve(B * m * n * 8),
-                 o_p0 = carve(B * m * 8), o_sp = carve(B * m * n * 8), o_s0 = carve(B * m * 8);
-    if (off > ctx->scratch_bytes) {
-        if (ctx->scratch) (void)hipFree(ctx->scratch);
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->scratch, off));
-        ctx->scratch_bytes = off;
-    }
-    char *base = (char *)ctx->scratch;
+    Staging S(ctx, "mipx_gomory_batch");
+    const size_t o_l = S.in(l, B * n * 8), o_u = S.in(u, B * n * 8), o_v = S.in(vstat, B * nv),
+                 o_x = S.in(x, B * n * 8), o_int = S.in(is_int, n), o_T = S.carve(B * m * n * 8),
+                 o_vec = S.carve(B * (n + 3 * m) * 8), o_idx = S.carve(B * (2 * n + m) * 4),
+                 o_nc = S.out(ncuts, B * 4), o_ri = S.out(row_idx, B * m * 4), o_pi = S.out(pi, B * m * n * 8),
+                 o_p0 = S.out(pi0, B * m * 8), o_sp = S.out(safe_pi, B * m * n * 8), o_s0 = S.out(safe_pi0, B * m * 8);
     hipStream_t st = ctx->stream;
-    int rc = MIPX_OK;
-    auto up = [&](size_t o, const void *src, size_t bytes) {
-        if (rc == MIPX_OK && hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-            rc = fail(ctx, MIPX_EHIP, "mipx_gomory_batch: upload");
-    };
-    up(o_l, l, B * n * 8); up(o_u, u, B * n * 8); up(o_v, vstat, B * nv); up(o_x, x, B * n * 8);
-    up(o_int, is_int, n);
+    int rc = S.alloc(ctx->scratch, ctx->scratch_bytes);
+    if (rc == MIPX_OK) rc = S.upload();
     if (rc == MIPX_OK) {
         // K1 from the given (optimal) basis: refactorises and leaves T / bvar / nvar in HBM
-        mipx::LpArgs a;
-        a.m = p->m; a.n = p->n;
-        a.A = p->dA; a.b = p->db; a.c = p->dc;
-        a.A_stride = a.b_stride = a.c_stride = 0;
-        a.l = (const double *)(base + o_l); a.u = (const double *)(base + o_u);
-        a.vstat_in = (const int8_t *)(base + o_v); a.slot = nullptr; a.max_iter = 0;
-        a.anchor_T = nullptr; a.anchor_vec = nullptr; a.anchor_idx = nullptr; a.refactor_only = 0;
-        a.status = nullptr; a.obj = nullptr; a.x = nullptr; a.y = nullptr; a.vstat_out = nullptr;
-        a.iters = nullptr; a.npivots = nullptr; a.batch = batch;
-        a.dbg_T = (double *)(base + o_T); a.dbg_vec = (double *)(base + o_vec);
-        a.dbg_idx = (int32_t *)(base + o_idx); a.dbg_all = 1;
+        mipx::LpArgs a = problem_args(p, false);
+        a.l = S.at<const double>(o_l); a.u = S.at<const double>(o_u);
+        a.vstat_in = S.at<const int8_t>(o_v); a.batch = batch;
+        a.dbg_T = S.at<double>(o_T); a.dbg_vec = S.at<double>(o_vec); a.dbg_idx = S.at<int32_t>(o_idx); a.dbg_all = 1;
         rc = launch_lp_any(p, a, batch);
     }
     if (rc == MIPX_OK) {
         mipx::GomoryArgs g;
         g.m = p->m; g.n = p->n; g.batch = batch;
         g.A = p->dA; g.b = p->db;
-        g.T = (const double *)(base + o_T); g.idx = (const int32_t *)(base + o_idx);
-        g.x = (const double *)(base + o_x); g.is_int = (const uint8_t *)(base + o_int);
+        g.T = S.at<const double>(o_T); g.idx = S.at<const int32_t>(o_idx);
+        g.x = S.at<const double>(o_x); g.is_int = S.at<const uint8_t>(o_int);
         g.max_term = max_term;
-        g.ncuts = (int32_t *)(base + o_nc); g.row_idx = (int32_t *)(base + o_ri);
-        g.pi = (double *)(base + o_pi); g.pi0 = (double *)(base + o_p0);
-        g.safe_pi = (double *)(base + o_sp); g.safe_pi0 = (double *)(base + o_s0);
+        g.ncuts = S.at<int32_t>(o_nc); g.row_idx = S.at<int32_t>(o_ri);
+        g.pi = S.at<double>(o_pi); g.pi0 = S.at<double>(o_p0);
+        g.safe_pi = S.at<double>(o_sp); g.safe_pi0 = S.at<double>(o_s0);
         g.chunks = batch >= 256 ? 1 : (batch >= 32 ? 4 : 16);  // (enough workgroups to use the GPU either way)
         g.group = mipx::gomory_group(p->n, p->m, (long)batch * g.chunks);
         g.mfma = (getenv("MIPX_K2_MFMA") && atoi(getenv("MIPX_K2_MFMA"))) ? 1 : 0;   // (experiment: cut_kernels.hip.h)
@@ -796,14 +736,7 @@ int mipx_gomory_batch(mipx_problem *p, int batch, const double *l, const double 
         hipLaunchKernelGGL((mipx::gomory_cuts<256>), dim3(batch * g.chunks), dim3(256), lds, st, g);
         if (hipGetLastError() != hipSuccess) rc = fail(ctx, MIPX_EHIP, "mipx_gomory_batch: launch");
     }
-    auto down = [&](void *dst, size_t o, size_t bytes) {
-        if (dst && rc == MIPX_OK && hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
-            rc = fail(ctx, MIPX_EHIP, "mipx_gomory_batch: download");
-    };
-    down(ncuts, o_nc, B * 4); down(row_idx, o_ri, B * m * 4); down(pi, o_pi, B * m * n * 8);
-    down(pi0, o_p0, B * m * 8); down(safe_pi, o_sp, B * m * n * 8); down(safe_pi0, o_s0, B * m * 8);
-    if (hipStreamSynchronize(st) != hipSuccess && rc == MIPX_OK) rc = fail(ctx, MIPX_EHIP, "mipx_gomory_batch: sync");
-    return rc;
+    return S.finish(rc);
 }
 
 int mipx_cut_select_batch(mipx_ctx *ctx, int n, int batch, int kmax, const int32_t *npool,
@@ -819,47 +752,26 @@ int mipx_cut_select_batch(mipx_ctx *ctx, int n, int batch, int kmax, const int32
         if (npool[k] < 0 || npool[k] > kmax) return fail(ctx, MIPX_EINVAL, "mipx_cut_select_batch: npool out of range");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, nn = (size_t)n, K = (size_t)kmax;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_np = carve(B * 4), o_pi = carve(B * K * nn * 8), o_p0 = carve(B * K * 8),
-                 o_x = carve(B * nn * 8), o_na = carve(B * 4), o_ad = carve(B * K * 4),
-                 o_te = carve(B * 4), o_de = carve(B * K * 8);
-    if (off > ctx->scratch_bytes) {
-        if (ctx->scratch) (void)hipFree(ctx->scratch);
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->scratch, off));
-        ctx->scratch_bytes = off;
-    }
-    char *base = (char *)ctx->scratch;
-    hipStream_t st = ctx->stream;
-    int rc = MIPX_OK;
-    auto up = [&](size_t o, const void *src, size_t bytes) {
-        if (rc == MIPX_OK && hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-            rc = fail(ctx, MIPX_EHIP, "mipx_cut_select_batch: upload");
-    };
-    up(o_np, npool, B * 4); up(o_pi, pi, B * K * nn * 8); up(o_p0, pi0, B * K * 8); up(o_x, x, B * nn * 8);
+    Staging S(ctx, "mipx_cut_select_batch");
+    const size_t o_np = S.in(npool, B * 4), o_pi = S.in(pi, B * K * nn * 8), o_p0 = S.in(pi0, B * K * 8),
+                 o_x = S.in(x, B * nn * 8), o_na = S.out(nadded, B * 4), o_ad = S.out(added, B * K * 4),
+                 o_te = S.out(terminator, B * 4), o_de = S.out(depth, B * K * 8);
+    int rc = S.alloc(ctx->scratch, ctx->scratch_bytes);
+    if (rc == MIPX_OK) rc = S.upload();
     if (rc == MIPX_OK) {
         mipx::SelectArgs g;
         g.n = n; g.batch = batch; g.kmax = kmax;
-        g.npool = (const int32_t *)(base + o_np); g.pi = (const double *)(base + o_pi);
-        g.pi0 = (const double *)(base + o_p0); g.x = (const double *)(base + o_x);
+        g.npool = S.at<const int32_t>(o_np); g.pi = S.at<const double>(o_pi);
+        g.pi0 = S.at<const double>(o_p0); g.x = S.at<const double>(o_x);
         g.max_nonzero_coefs = max_nonzero_coefs; g.min_cut_depth = min_cut_depth;
         g.cos_parallel = cos_parallel; g.max_abs_coef = max_abs_coef;
-        g.nadded = (int32_t *)(base + o_na); g.added = (int32_t *)(base + o_ad);
-        g.terminator = (int32_t *)(base + o_te); g.depth = (double *)(base + o_de);
+        g.nadded = S.at<int32_t>(o_na); g.added = S.at<int32_t>(o_ad);
+        g.terminator = S.at<int32_t>(o_te); g.depth = S.at<double>(o_de);
         const size_t lds = K * (3 * 8 + 2 * 4) + 16 + 64;
-        hipLaunchKernelGGL(mipx::select_cuts, dim3(batch), dim3(256), lds, st, g);
+        hipLaunchKernelGGL(mipx::select_cuts, dim3(batch), dim3(256), lds, ctx->stream, g);
         if (hipGetLastError() != hipSuccess) rc = fail(ctx, MIPX_EHIP, "mipx_cut_select_batch: launch");
     }
-    auto down = [&](void *dst, size_t o, size_t bytes) {
-        if (dst && rc == MIPX_OK && hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
-            rc = fail(ctx, MIPX_EHIP, "mipx_cut_select_batch: download");
-    };
-    down(nadded, o_na, B * 4); down(added, o_ad, B * K * 4); down(terminator, o_te, B * 4);
-    down(depth, o_de, B * K * 8);
-    if (hipStreamSynchronize(st) != hipSuccess && rc == MIPX_OK) rc = fail(ctx, MIPX_EHIP, "mipx_cut_select_batch: sync");
-    return rc;
+    return S.finish(rc);
 }
 
 int mipx_safe_cut_batch(mipx_ctx *ctx, int n, int batch, const double *pi, const double *pi0,
@@ -872,43 +784,25 @@ int mipx_safe_cut_batch(mipx_ctx *ctx, int n, int batch, const double *pi, const
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, nn = (size_t)n;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_pi = carve(B * nn * 8), o_p0 = carve(B * 8), o_sp = carve(B * nn * 8), o_s0 = carve(B * 8),
-                 o_nu = carve(B * (nn + 1) * 8), o_de = carve(B * (nn + 1) * 8), o_cp = carve(B * nn * 8),
-                 o_c0 = carve(B * 8), o_nz = carve(B * 4);
-    if (off > ctx->scratch_bytes) {
-        if (ctx->scratch) (void)hipFree(ctx->scratch);
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->scratch, off));
-        ctx->scratch_bytes = off;
+    Staging S(ctx, "mipx_safe_cut_batch");
+    const size_t o_pi = S.in(pi, B * nn * 8), o_p0 = S.in(pi0, B * 8), o_sp = S.out(safe_pi, B * nn * 8),
+                 o_s0 = S.out(safe_pi0, B * 8), o_nu = S.out(num, B * (nn + 1) * 8), o_de = S.out(den, B * (nn + 1) * 8),
+                 o_cp = S.out(scaled_pi, B * nn * 8), o_c0 = S.out(scaled_pi0, B * 8), o_nz = S.out(nonzero, B * 4);
+    int rc = S.alloc(ctx->scratch, ctx->scratch_bytes);
+    if (rc == MIPX_OK) rc = S.upload();
+    if (rc == MIPX_OK) {
+        mipx::SafeCutArgs g;
+        g.n = n; g.batch = batch;
+        g.pi = S.at<const double>(o_pi); g.pi0 = S.at<const double>(o_p0);
+        g.estimate = estimate; g.make_integer = make_integer ? 1 : 0; g.max_term = max_term;
+        g.safe_pi = S.at<double>(o_sp); g.safe_pi0 = S.at<double>(o_s0);
+        g.num = S.at<double>(o_nu); g.den = S.at<double>(o_de);
+        g.scaled_pi = S.at<double>(o_cp); g.scaled_pi0 = S.at<double>(o_c0);
+        g.nonzero = S.at<int32_t>(o_nz);
+        hipLaunchKernelGGL(mipx::safe_cut_batch, dim3(batch), dim3(256), 0, ctx->stream, g);
+        if (hipError_t e = hipGetLastError()) rc = S.err("launch", e);
     }
-    char *base = (char *)ctx->scratch;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_pi, pi, B * nn * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_p0, pi0, B * 8, hipMemcpyHostToDevice, st));
-    mipx::SafeCutArgs g;
-    g.n = n; g.batch = batch;
-    g.pi = (const double *)(base + o_pi); g.pi0 = (const double *)(base + o_p0);
-    g.estimate = estimate; g.make_integer = make_integer ? 1 : 0; g.max_term = max_term;
-    g.safe_pi = (double *)(base + o_sp); g.safe_pi0 = (double *)(base + o_s0);
-    g.num = (double *)(base + o_nu); g.den = (double *)(base + o_de);
-    g.scaled_pi = (double *)(base + o_cp); g.scaled_pi0 = (double *)(base + o_c0);
-    g.nonzero = (int32_t *)(base + o_nz);
-    hipLaunchKernelGGL(mipx::safe_cut_batch, dim3(batch), dim3(256), 0, st, g);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(safe_pi, base + o_sp, B * nn * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(safe_pi0, base + o_s0, B * 8, hipMemcpyDeviceToHost, st));
-    if (num) {
-        HIP_TRY(ctx, hipMemcpyAsync(num, base + o_nu, B * (nn + 1) * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(den, base + o_de, B * (nn + 1) * 8, hipMemcpyDeviceToHost, st));
-    }
-    if (scaled_pi) HIP_TRY(ctx, hipMemcpyAsync(scaled_pi, base + o_cp, B * nn * 8, hipMemcpyDeviceToHost, st));
-    if (scaled_pi0) HIP_TRY(ctx, hipMemcpyAsync(scaled_pi0, base + o_c0, B * 8, hipMemcpyDeviceToHost, st));
-    if (nonzero) HIP_TRY(ctx, hipMemcpyAsync(nonzero, base + o_nz, B * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return MIPX_OK;
+    return S.finish(rc);
 }
 
 int mipx_get_fraction_batch(mipx_ctx *ctx, int count, const double *x, const double *max_term,
@@ -921,32 +815,21 @@ int mipx_get_fraction_batch(mipx_ctx *ctx, int count, const double *x, const dou
             return fail(ctx, MIPX_EINVAL, "mipx_get_fraction_batch: estimate must be 0..2, max_term positive");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)count;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_x = carve(N * 8), o_mt = carve(N * 8), o_es = carve(N * 4), o_nu = carve(N * 8), o_de = carve(N * 8);
-    if (off > ctx->scratch_bytes) {
-        if (ctx->scratch) (void)hipFree(ctx->scratch);
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->scratch, off));
-        ctx->scratch_bytes = off;
+    Staging S(ctx, "mipx_get_fraction_batch");
+    const size_t o_x = S.in(x, N * 8), o_mt = S.in(max_term, N * 8), o_es = S.in(estimate, N * 4),
+                 o_nu = S.out(num, N * 8), o_de = S.out(den, N * 8);
+    int rc = S.alloc(ctx->scratch, ctx->scratch_bytes);
+    if (rc == MIPX_OK) rc = S.upload();
+    if (rc == MIPX_OK) {
+        mipx::FractionArgs g;
+        g.count = count;
+        g.x = S.at<const double>(o_x); g.max_term = S.at<const double>(o_mt);
+        g.estimate = S.at<const int32_t>(o_es);
+        g.num = S.at<double>(o_nu); g.den = S.at<double>(o_de);
+        hipLaunchKernelGGL(mipx::get_fraction_batch, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, g);
+        if (hipError_t e = hipGetLastError()) rc = S.err("launch", e);
     }
-    char *base = (char *)ctx->scratch;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_x, x, N * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_mt, max_term, N * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_es, estimate, N * 4, hipMemcpyHostToDevice, st));
-    mipx::FractionArgs g;
-    g.count = count;
-    g.x = (const double *)(base + o_x); g.max_term = (const double *)(base + o_mt);
-    g.estimate = (const int32_t *)(base + o_es);
-    g.num = (double *)(base + o_nu); g.den = (double *)(base + o_de);
-    hipLaunchKernelGGL(mipx::get_fraction_batch, dim3((count + 255) / 256), dim3(256), 0, st, g);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(num, base + o_nu, N * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(den, base + o_de, N * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return MIPX_OK;
+    return S.finish(rc);
 }
 
 int mipx_branch_score_batch_dev(mipx_ctx *ctx, int n, int batch, int n_int, const int32_t *int_idx,
@@ -984,37 +867,19 @@ int mipx_branch_score_batch(mipx_ctx *ctx, int n, int batch, int n_int, const in
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, nn = (size_t)n, ni = (size_t)(n_int ? n_int : 1);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_ii = carve(ni * 4), o_x = carve(B * nn * 8), o_st = carve(B * 4), o_cl = carve(nn * 8),
-                 o_cr = carve(nn * 8), o_he = carve(nn), o_bi = carve(B * 4), o_mf = carve(B * 4), o_np = carve(B * 4);
-    if (off > ctx->scratch_bytes) {
-        if (ctx->scratch) (void)hipFree(ctx->scratch);
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->scratch, off));
-        ctx->scratch_bytes = off;
-    }
-    char *base = (char *)ctx->scratch;
-    hipStream_t st = ctx->stream;
-    if (n_int) HIP_TRY(ctx, hipMemcpyAsync(base + o_ii, int_idx, (size_t)n_int * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_x, x, B * nn * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_st, status, B * 4, hipMemcpyHostToDevice, st));
-    if (rule == 1) {
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_cl, cost_l, nn * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_cr, cost_r, nn * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_he, has_entry, nn, hipMemcpyHostToDevice, st));
-    }
-    int rc = mipx_branch_score_batch_dev(
-        ctx, n, batch, n_int, (const int32_t *)(base + o_ii), (const double *)(base + o_x),
-        (const int32_t *)(base + o_st), rule, (const double *)(base + o_cl), (const double *)(base + o_cr),
-        (const uint8_t *)(base + o_he), (int32_t *)(base + o_bi), (int32_t *)(base + o_mf), (int32_t *)(base + o_np));
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(branch_idx, base + o_bi, B * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(mip_feasible, base + o_mf, B * 4, hipMemcpyDeviceToHost, st));
-    if (n_unprobed) HIP_TRY(ctx, hipMemcpyAsync(n_unprobed, base + o_np, B * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return MIPX_OK;
+    Staging S(ctx, "mipx_branch_score_batch");
+    const size_t o_ii = S.carve(ni * 4);
+    S.up(o_ii, n_int ? int_idx : nullptr, (size_t)n_int * 4);
+    const size_t o_x = S.in(x, B * nn * 8), o_st = S.in(status, B * 4), o_cl = S.in(rule == 1 ? cost_l : nullptr, nn * 8),
+                 o_cr = S.in(rule == 1 ? cost_r : nullptr, nn * 8), o_he = S.in(rule == 1 ? has_entry : nullptr, nn),
+                 o_bi = S.out(branch_idx, B * 4), o_mf = S.out(mip_feasible, B * 4), o_np = S.out(n_unprobed, B * 4);
+    int rc = S.alloc(ctx->scratch, ctx->scratch_bytes);
+    if (rc == MIPX_OK) rc = S.upload();
+    if (rc == MIPX_OK)
+        rc = mipx_branch_score_batch_dev(ctx, n, batch, n_int, S.at<const int32_t>(o_ii), S.at<const double>(o_x),
+                                         S.at<const int32_t>(o_st), rule, S.at<const double>(o_cl), S.at<const double>(o_cr),
+                                         S.at<const uint8_t>(o_he), S.at<int32_t>(o_bi), S.at<int32_t>(o_mf), S.at<int32_t>(o_np));
+    return S.finish(rc);
 }
 
 int mipx_dev_alloc(mipx_ctx *ctx, size_t bytes, void **dptr) {

@@ -481,7 +481,7 @@ int launch_lp(mipx_tree *t, int batch, const double *l, const double *u, const i
               const int32_t *slot, int max_iter, int32_t *status, double *obj, double *x,
               int8_t *vout, int32_t *iters, int32_t *npiv, hipStream_t stream = nullptr,
               const StepBuf *dive = nullptr, const int32_t *asel = nullptr, const CutLaunch *cl = nullptr) {
-    mipx::LpArgs a;
+    mipx::LpArgs a = problem_args(t->prob, !(cl != nullptr && cl->no_anchor));
     if (dive) {  // in-place dive: K4's rule inside K1, level p's children at positions p * batch ..
         a.dive = dive->dive; a.dive_off = batch; a.rule = t->rule; a.n_int = t->n_int;
         const TabPtr tb = tab_at(t, t->fast_ok ? t->tab_host : 0);
@@ -491,22 +491,14 @@ int launch_lp(mipx_tree *t, int batch, const double *l, const double *u, const i
         a.dive_preset = 1;           // the kernel itself marks "no child / no dive" first
         a.zero16 = dive->d_ask_count; // and zeroes K4's request counter
     }
-    a.m = t->m; a.n = t->n;
-    a.A = t->prob->dA; a.b = t->prob->db; a.c = t->prob->dc;
-    a.A_stride = a.b_stride = a.c_stride = 0;
     a.l = l; a.u = u; a.vstat_in = v; a.slot = slot; a.max_iter = max_iter;
     a.cold = t->cold_launch ? 1 : 0;   // (the root's step: its pool row holds no basis)
     t->cold_launch = false;
-    a.anchor_T = t->prob->anchor_on ? t->prob->anchor_T : nullptr;
-    a.anchor_vec = t->prob->anchor_on ? t->prob->anchor_vec : nullptr;
-    a.anchor_idx = t->prob->anchor_on ? t->prob->anchor_idx : nullptr;
     if (asel != nullptr && t->atab_T != nullptr) {  // node LPs: the anchor their record names
         a.anchor_sel = asel; a.atab_T = t->atab_T; a.atab_vec = t->atab_vec; a.atab_idx = t->atab_idx;
     }
-    a.refactor_only = 0;
-    a.status = status; a.obj = obj; a.x = x; a.y = nullptr; a.vstat_out = vout;
+    a.status = status; a.obj = obj; a.x = x; a.vstat_out = vout;
     a.iters = iters; a.npivots = npiv; a.batch = batch;
-    a.dbg_T = nullptr; a.dbg_vec = nullptr; a.dbg_idx = nullptr; a.dbg_all = 0;
     int m_rows = -1;
     if (cl != nullptr) {
         a.ncut = cl->ncut; a.cut_ids = cl->ids; a.cut_stride = t->kc;
@@ -514,7 +506,6 @@ int launch_lp(mipx_tree *t, int batch, const double *l, const double *u, const i
         a.mstride = t->mrows; a.vstat_by_node = cl->vstat_by_node; a.active = cl->active;
         a.y = cl->y;
         if (cl->dT) { a.dbg_T = cl->dT; a.dbg_vec = cl->dvec; a.dbg_idx = cl->didx; a.dbg_all = 1; }
-        if (cl->no_anchor) { a.anchor_T = nullptr; a.anchor_vec = nullptr; a.anchor_idx = nullptr; }
         m_rows = cl->m_rows;
     }
     return launch_lp_any(t->prob, a, batch, stream, m_rows);
@@ -2397,11 +2388,8 @@ int mipx_tree_reanchor(mipx_tree *t, int64_t max_nodes) {
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(d_sl, sl.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
     // refactor-only solves of the K nodes (from the anchors they have now), every final tableau dumped
-    mipx::LpArgs a;
-    a.m = t->m; a.n = t->n;
-    a.A = t->prob->dA; a.b = t->prob->db; a.c = t->prob->dc;
-    a.A_stride = a.b_stride = a.c_stride = 0;
-    a.l = t->pool_l; a.u = t->pool_u; a.vstat_in = t->pool_v; a.slot = d_sl; a.max_iter = 0;
+    mipx::LpArgs a = problem_args(t->prob);
+    a.l = t->pool_l; a.u = t->pool_u; a.vstat_in = t->pool_v; a.slot = d_sl;
     double *gl = nullptr, *gu = nullptr;
     int8_t *gv = nullptr;
     if (t->cuts) {   // (the pool's basis rows are n + mrows wide: dense copies over the shared rows)
@@ -2414,13 +2402,8 @@ int mipx_tree_reanchor(mipx_tree *t, int64_t max_nodes) {
         hipLaunchKernelGGL(mipx::gather_plain_nodes, dim3((unsigned)K), dim3(256), 0, st, ga);
         a.l = gl; a.u = gu; a.vstat_in = gv; a.slot = nullptr;
     }
-    a.anchor_T = t->prob->anchor_on ? t->prob->anchor_T : nullptr;
-    a.anchor_vec = t->prob->anchor_on ? t->prob->anchor_vec : nullptr;
-    a.anchor_idx = t->prob->anchor_on ? t->prob->anchor_idx : nullptr;
     if (t->atab_T != nullptr) { a.anchor_sel = d_sl + K; a.atab_T = t->atab_T; a.atab_vec = t->atab_vec; a.atab_idx = t->atab_idx; }
-    a.refactor_only = 1;
-    a.status = nullptr; a.obj = nullptr; a.x = nullptr; a.y = nullptr; a.vstat_out = nullptr;
-    a.iters = nullptr; a.npivots = nullptr; a.batch = (int)K;
+    a.refactor_only = 1; a.batch = (int)K;
     a.dbg_T = nT; a.dbg_vec = nvec; a.dbg_idx = nidx; a.dbg_all = 1;
     int rc = launch_lp_any(t->prob, a, (int)K, st);
     if (rc == MIPX_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(ctx, MIPX_EHIP, "mipx_tree_reanchor: launch failed");

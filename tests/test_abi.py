@@ -1,5 +1,6 @@
 """The C-ABI library loads and exports every symbol include/mipx.h declares (no compute calls:
 this runs where there is no GPU), and fails loudly instead of falling back."""
+import ctypes as C
 import os
 import re
 
@@ -18,6 +19,36 @@ def declared_symbols():
 
 def test_header_and_binding_agree():
     assert declared_symbols() == sorted(_ffi.SYMBOLS)
+
+
+def declared_prototypes():
+    """{name: (return type, [parameter declarations])} of every function include/mipx.h declares."""
+    text = open(os.path.join(ROOT, 'include', 'mipx.h')).read()
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    found = re.findall(r'([\w ]+?[\s*]+)(mipx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;', text)
+    return {name: (ret.strip(), [p.strip() for p in args.split(',') if p.strip() not in ('', 'void')])
+            for ret, name, args in found}
+
+
+def test_signature_table_matches_the_header():
+    """Every _ffi._SIGNATURES entry has the header's arity, parameter types and return type (no library
+    load: a wrong c_int against an int64_t / size_t or a missing restype shows here)."""
+    scalars = {'int': C.c_int, 'int64_t': C.c_int64, 'size_t': C.c_size_t, 'double': C.c_double,
+               'void': None, 'mipx_tree_hook': _ffi.TREE_HOOK}
+
+    def agrees(decl, ctype):
+        if '*' in decl or '[' in decl:   # any pointer, array parameter or opaque handle
+            return ctype in (C.c_void_p, C.c_char_p) or (isinstance(ctype, type) and issubclass(ctype, C._Pointer))
+        return ctype is scalars[decl.replace('const ', '').split()[0]]
+
+    protos = declared_prototypes()
+    assert len(protos) == len(_ffi._SIGNATURES) == 70
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _ffi._SIGNATURES[name]
+        assert agrees(ret, restype), f'{name} returns {ret}, the table says {restype}'
+        assert len(params) == len(argtypes), f'{name}: {len(params)} parameters, the table has {len(argtypes)}'
+        for k, (decl, ctype) in enumerate(zip(params, argtypes)):
+            assert agrees(decl, ctype), f'{name} parameter {k} is `{decl}`, the table says {ctype}'
 
 
 def test_library_exports_every_declared_symbol():
