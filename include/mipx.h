@@ -521,4 +521,7 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #ifdef __cplusplus
 }
 #endif
+
+#include "mipx_spill.h"   /* host spill of the frontier engine and its compact node records */
+
 #endif /* MIPX_H */

@@ -193,6 +193,18 @@ _SIGNATURES = {
 }
 SYMBOLS = list(_SIGNATURES)   # (tests/test_abi.py: the header declares exactly these)
 
+# ... and those of include/mipx_spill.h (host spill of the frontier engine), which mipx.h includes
+# (tests/test_node_spill_abi.py checks them against that header)
+_SPILL_SIGNATURES = {
+    'mipx_node_pack_batch': (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i, _vp, _vp, _i64, _vp]),
+    'mipx_node_unpack_batch': (_i, [_vp, _i, _i, _i] + [_vp] * 9 + [_i]),
+    'mipx_tree_set_host_spill': (_i, [_vp, _i64]),
+    'mipx_tree_spill_stats': (_i, [_vp, _vp]),
+}
+SPILL_SYMBOLS = list(_SPILL_SIGNATURES)
+SPILL_STATS_KEYS = ('spilled', 'reloaded', 'on_host', 'host_bytes', 'peak_host_bytes', 'events', 'spill_ms',
+                    'reload_ms')
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -205,7 +217,7 @@ def lib():
             f'(run `make -C {os.path.dirname(LIB_PATH)}` or __graft_entry__.build()). '
             'simple_mip_solver_amd has no CPU fallback.')
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_SPILL_SIGNATURES.items()):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -434,6 +446,56 @@ def get_fraction_batch(ctx, x, max_term, estimate):
     rc = lib().mipx_get_fraction_batch(ctx._h, len(x), _ptr(x), _ptr(mt), _ptr(est), _ptr(num), _ptr(den))
     ctx.check(rc, 'mipx_get_fraction_batch')
     return num.astype(np.int64), den.astype(np.int64)
+
+
+def node_pack_batch(ctx, root_l, root_u, l, u, vstat, ncut=None, cut_ids=None):
+    """Compact records (include/mipx_spill.h) of count rows: (offsets int64 count + 1, bytes uint8).
+    Cut mode when ncut / cut_ids (count x kcut) are given."""
+    l = np.ascontiguousarray(l, np.float64)
+    u = np.ascontiguousarray(u, np.float64)
+    vstat = np.ascontiguousarray(vstat, np.int8)
+    count, n = l.shape
+    nv = vstat.shape[1]
+    kcut = 0
+    if cut_ids is not None:
+        cut_ids = np.ascontiguousarray(cut_ids, np.int32)
+        ncut = np.ascontiguousarray(ncut, np.int32)
+        kcut = cut_ids.shape[1]
+    rl = np.ascontiguousarray(root_l, np.float64)
+    ru = np.ascontiguousarray(root_u, np.float64)
+    off = np.zeros(count + 1, np.int64)
+    used = np.zeros(1, np.int64)
+    L = lib()
+    rc = L.mipx_node_pack_batch(ctx._h, n, nv, count, _ptr(rl), _ptr(ru), _ptr(l), _ptr(u), _ptr(vstat),
+                                _ptr(ncut) if kcut else None, _ptr(cut_ids) if kcut else None, kcut, _ptr(off),
+                                None, 0, _ptr(used))
+    if rc != -5:   # (MIPX_ENOMEM with cap 0: *used says how much room the records take)
+        ctx.check(rc, 'mipx_node_pack_batch')
+    out = np.zeros(max(int(used[0]), 1), np.uint8)
+    rc = L.mipx_node_pack_batch(ctx._h, n, nv, count, _ptr(rl), _ptr(ru), _ptr(l), _ptr(u), _ptr(vstat),
+                                _ptr(ncut) if kcut else None, _ptr(cut_ids) if kcut else None, kcut, _ptr(off),
+                                _ptr(out), out.size, _ptr(used))
+    ctx.check(rc, 'mipx_node_pack_batch')
+    return off, out[:int(used[0])]
+
+
+def node_unpack_batch(ctx, root_l, root_u, offsets, records, nv, kcut=0, cut_ids=None):
+    """Rows (l, u, vstat[, ncut, cut_ids]) back from compact records; cut_ids (count x kcut) gives the values
+    left beyond each node's ncut."""
+    rl = np.ascontiguousarray(root_l, np.float64)
+    ru = np.ascontiguousarray(root_u, np.float64)
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    records = np.ascontiguousarray(records, np.uint8)
+    n, count = rl.size, offsets.size - 1
+    l, u = np.zeros((count, n)), np.zeros((count, n))
+    v = np.zeros((count, nv), np.int8)
+    ncut = np.zeros(count, np.int32)
+    ids = np.zeros((count, max(kcut, 1)), np.int32) if cut_ids is None else np.array(cut_ids, np.int32)
+    rc = lib().mipx_node_unpack_batch(ctx._h, n, nv, count, _ptr(rl), _ptr(ru), _ptr(offsets), _ptr(records),
+                                      _ptr(l), _ptr(u), _ptr(v), _ptr(ncut) if kcut else None,
+                                      _ptr(ids) if kcut else None, kcut)
+    ctx.check(rc, 'mipx_node_unpack_batch')
+    return (l, u, v, ncut, ids) if kcut else (l, u, v)
 
 
 def branch_score_batch(ctx, integer_indices, x, status, rule=0, cost_l=None, cost_r=None, has_entry=None):
@@ -794,6 +856,21 @@ class Tree:
         tl = np.ascontiguousarray(tl, np.int32); tr = np.ascontiguousarray(tr, np.int32)
         self.problem.ctx.check(lib().mipx_tree_set_pseudo_costs(self._h, _ptr(cl), _ptr(cr), _ptr(tl), _ptr(tr)),
                                'mipx_tree_set_pseudo_costs')
+
+    def set_host_spill(self, max_bytes):
+        """Spill open nodes to pinned host memory, up to max_bytes of compact records, when the pool runs
+        low, instead of stopping the search (mipx_tree_set_host_spill; 0 turns it off)."""
+        self.problem.ctx.check(lib().mipx_tree_set_host_spill(self._h, int(max_bytes)), 'mipx_tree_set_host_spill')
+
+    def spill_stats(self):
+        """dict(spilled, reloaded, on_host, host_bytes, peak_host_bytes, events, spill_ms, reload_ms)
+        (mipx_tree_spill_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_spill_stats(self._h, _ptr(out)), 'mipx_tree_spill_stats')
+        d = dict(zip(SPILL_STATS_KEYS, (int(v) for v in out)))
+        d['spill_ms'] /= 1000.0
+        d['reload_ms'] /= 1000.0
+        return d
 
     def peek_open(self, max_nodes):
         """(l, u, vstat, dual_bound) of up to max_nodes open nodes, without removing them."""

@@ -12,6 +12,7 @@ re-scanning every tree vertex up to four times per iteration (reference :199-213
 same value, O(log N) instead of O(N).
 """
 import heapq
+import os
 from queue import PriorityQueue
 import time
 
@@ -122,7 +123,8 @@ class BranchAndBound(BaseAlgorithm):
 
     def __init__(self, model, Node=BaseNode, node_queue=None, node_limit=INF, mip_gap=.0001,
                  logging=False, max_run_time=INF, initial_primal_bound=INF, frontier_batch=None,
-                 lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5, **kwargs):
+                 lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
+                 host_spill=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -152,7 +154,15 @@ class BranchAndBound(BaseAlgorithm):
         it only if the LP is still exactly what was solved (rows, bounds, basis, iteration limit), and
         solves as before otherwise.  Cut-round re-solves, strong-branching probes and LPs with free
         columns stay per node.  lp_batch=1 evaluates the same nodes as the default; a larger batch
-        finds the same status and optimum in another order.  Counters: `lp_batch_stats`."""
+        finds the same status and optimum in another order.  Counters: `lp_batch_stats`.
+        host_spill (extension; needs frontier_batch, not with comm; default None = off): when the
+        device node pool runs low, the open nodes the queue pops last move to pinned host memory as
+        compact records and come back when they are popped, so the search goes on instead of stopping
+        (include/mipx_spill.h).  The nodes evaluated and their order are those of a pool that never
+        fills.  True caps the host store at half of the physical memory, an int at that many bytes; the
+        search stops (RuntimeWarning, as with a full pool) only when the cap is reached.  pool_capacity
+        must be at least 2 H + 1 rows, H = 3 x frontier_batch x (2 (1 + dive) + 1) (x 1 for
+        frontier_batch = 1).  Counters: `spill_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -166,6 +176,15 @@ class BranchAndBound(BaseAlgorithm):
         self._native = None
         self._native_stats = None
         assert comm is None or frontier_batch is not None, 'comm needs frontier_batch'
+        assert host_spill is None or host_spill is True or (
+            isinstance(host_spill, int) and not isinstance(host_spill, bool) and host_spill > 0), \
+            'host_spill is None, True or a positive number of bytes'
+        assert host_spill is None or frontier_batch is not None, 'host_spill needs frontier_batch'
+        assert host_spill is None or comm is None, 'host_spill cannot be combined with comm'
+        if host_spill is True:
+            host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
+        self._host_spill = host_spill
+        self.spill_stats = None
         self._comm, self._exchange_every, self._sharded = comm, exchange_every, False
         if frontier_batch is not None:
             assert isinstance(frontier_batch, int) and frontier_batch > 0, \
@@ -326,6 +345,8 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_anchor_mode(True)
             if self._dive:
                 self._native.set_dive(self._dive)
+            if self._host_spill:
+                self._native.set_host_spill(self._host_spill)
         st = None
         if self._comm is not None and not self._sharded:
             from simple_mip_solver_amd.parallel import shard_and_attach
@@ -344,10 +365,17 @@ class BranchAndBound(BaseAlgorithm):
             st = dict(st, evaluated_nodes=g['evaluated_nodes'])
             self._native_global = g
         self._native_stats = st
+        if self._host_spill:
+            self.spill_stats = self._native.spill_stats()
         if st['pool_exhausted']:
             import warnings
-            warnings.warn('the GPU node pool is full (pool_capacity=%d): the search stopped with the bounds '
-                          'found so far; pass a larger pool_capacity' % self._pool_capacity, RuntimeWarning)
+            if self._host_spill:
+                warnings.warn('the GPU node pool and the host spill store are full (pool_capacity=%d, host_spill=%d '
+                              'bytes): the search stopped with the bounds found so far; pass a larger host_spill'
+                              % (self._pool_capacity, self._host_spill), RuntimeWarning)
+            else:
+                warnings.warn('the GPU node pool is full (pool_capacity=%d): the search stopped with the bounds '
+                              'found so far; pass a larger pool_capacity' % self._pool_capacity, RuntimeWarning)
         self.solve_time = st['solve_seconds']
         self.evaluated_nodes = st['evaluated_nodes']
         self.primal_bound = st['primal_bound']

@@ -334,6 +334,7 @@ struct Staging {
 
 #include "cut_kernels.hip.h"
 #include "comm.hip.h"
+#include "spill_kernels.hip.h"
 #include "tree_engine.hip.h"
 
 extern "C" {
@@ -939,6 +940,100 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen) {
     if (!buf || buflen == 0) return MIPX_EINVAL;
     std::snprintf(buf, buflen, "%s", cfg ? cfg->name : "lp_dual_simplex_big");
     return MIPX_OK;
+}
+
+int mipx_node_pack_batch(mipx_ctx *ctx, int n, int nv, int count, const double *root_l, const double *root_u,
+                         const double *l, const double *u, const int8_t *vstat, const int32_t *ncut,
+                         const int32_t *cut_ids, int kcut, int64_t *out_offsets, void *out_bytes, int64_t cap,
+                         int64_t *used) {
+    if (!ctx) return MIPX_EINVAL;
+    if (n < 1 || nv < 1 || count < 0 || kcut < 0 || !root_l || !root_u || !out_offsets || !used || cap < 0 ||
+        (cap > 0 && !out_bytes) || (count > 0 && (!l || !u || !vstat || (kcut > 0 && (!ncut || !cut_ids)))))
+        return fail(ctx, MIPX_EINVAL, "mipx_node_pack_batch: bad argument");
+    for (int k = 0; kcut > 0 && k < count; k++)
+        if (ncut[k] < 0 || ncut[k] > kcut) return fail(ctx, MIPX_EINVAL, "mipx_node_pack_batch: ncut out of range");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)count, kc = (size_t)kcut;
+    // the largest records possible: every column a diff, every cut row carried
+    const size_t most = B * (size_t)mipx::spill_record_bytes(n, kcut, nv, kcut);
+    Staging S(ctx, "mipx_node_pack_batch");
+    const size_t o_rl = S.in(root_l, (size_t)n * 8), o_ru = S.in(root_u, (size_t)n * 8), o_l = S.in(l, B * n * 8),
+                 o_u = S.in(u, B * n * 8), o_v = S.in(vstat, B * nv), o_nc = S.in(kcut ? ncut : nullptr, B * 4),
+                 o_id = S.in(kcut ? cut_ids : nullptr, B * kc * 4), o_off = S.carve((B + 1) * 8), o_rec = S.carve(most);
+    int rc = S.alloc();
+    if (rc == MIPX_OK) rc = S.upload();
+    mipx::SpillArgs a;
+    a.n = n; a.nv = nv; a.kc = kcut; a.count = count;
+    a.root_l = S.at<const double>(o_rl); a.root_u = S.at<const double>(o_ru);
+    a.l = S.at<double>(o_l); a.u = S.at<double>(o_u); a.v = S.at<int8_t>(o_v);
+    a.ncut = S.at<int32_t>(o_nc); a.ids = S.at<int32_t>(o_id); a.off = S.at<int64_t>(o_off); a.rec = S.at<char>(o_rec);
+    hipStream_t st = ctx->stream;
+    if (rc == MIPX_OK && count > 0) {
+        hipLaunchKernelGGL(mipx::spill_count, dim3((count + 3) / 4), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(mipx::spill_scan, dim3(1), dim3(1024), 0, st, a);
+        hipLaunchKernelGGL(mipx::spill_pack, dim3((count + 3) / 4), dim3(256), 0, st, a);
+        if (hipError_t e = hipGetLastError()) rc = S.err("launch", e);
+    }
+    if (count == 0 && rc == MIPX_OK && hipMemsetAsync(a.off, 0, 8, st) != hipSuccess) rc = S.err("memset", hipGetLastError());
+    int64_t total = 0;
+    if (rc == MIPX_OK && hipMemcpyAsync(&total, a.off + B, 8, hipMemcpyDeviceToHost, st) != hipSuccess) rc = S.err("download", hipGetLastError());
+    if (rc == MIPX_OK && hipStreamSynchronize(st) != hipSuccess) rc = S.err("sync", hipGetLastError());
+    if (rc == MIPX_OK) {
+        *used = total;
+        if (total > cap) rc = MIPX_ENOMEM;   // (nothing but *used: the caller retries with room)
+        else {
+            S.down(out_offsets, o_off, (B + 1) * 8);
+            S.down(out_bytes, o_rec, (size_t)total);
+        }
+    }
+    rc = S.finish(rc);
+    return rc == MIPX_ENOMEM ? fail(ctx, MIPX_ENOMEM, "mipx_node_pack_batch: out_bytes too small (see *used)") : rc;
+}
+
+int mipx_node_unpack_batch(mipx_ctx *ctx, int n, int nv, int count, const double *root_l, const double *root_u,
+                           const int64_t *offsets, const void *in_bytes, double *l, double *u, int8_t *vstat,
+                           int32_t *ncut, int32_t *cut_ids, int kcut) {
+    if (!ctx) return MIPX_EINVAL;
+    if (n < 1 || nv < 1 || count < 0 || kcut < 0 || !root_l || !root_u || !offsets ||
+        (count > 0 && (!in_bytes || !l || !u || !vstat || (kcut > 0 && (!ncut || !cut_ids)))))
+        return fail(ctx, MIPX_EINVAL, "mipx_node_unpack_batch: bad argument");
+    if (count == 0) return MIPX_OK;
+    const size_t B = (size_t)count, kc = (size_t)kcut;
+    // the records are checked against their own headers before any kernel reads them
+    const char *rec = (const char *)in_bytes;
+    if (offsets[0] != 0) return fail(ctx, MIPX_EINVAL, "mipx_node_unpack_batch: offsets[0] must be 0");
+    for (size_t k = 0; k < B; k++) {
+        const int64_t o = offsets[k], len = offsets[k + 1] - o;
+        if (o % 8 != 0 || len < 16) return fail(ctx, MIPX_EINVAL, "mipx_node_unpack_batch: bad offsets");
+        int32_t hd[2];
+        std::memcpy(hd, rec + o + 8, 8);
+        if (hd[0] < 0 || hd[0] > n || hd[1] < 0 || (kcut > 0 ? hd[1] > kcut : hd[1] != 0) ||
+            mipx::spill_record_bytes(hd[0], hd[1], nv, kcut) != len)
+            return fail(ctx, MIPX_EINVAL, "mipx_node_unpack_batch: a record disagrees with its header");
+        const int32_t *col = (const int32_t *)(rec + o + 16);
+        for (int32_t q = 0; q < hd[0]; q++)
+            if (col[q] < 0 || col[q] >= n || (q > 0 && col[q] <= col[q - 1]))
+                return fail(ctx, MIPX_EINVAL, "mipx_node_unpack_batch: diff columns must ascend within [0, n)");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Staging S(ctx, "mipx_node_unpack_batch");
+    const size_t o_rl = S.in(root_l, (size_t)n * 8), o_ru = S.in(root_u, (size_t)n * 8), o_off = S.in(offsets, (B + 1) * 8),
+                 o_rec = S.in(in_bytes, (size_t)offsets[B]), o_l = S.out(l, B * n * 8), o_u = S.out(u, B * n * 8),
+                 o_v = S.out(vstat, B * nv), o_nc = S.out(kcut ? ncut : nullptr, B * 4),
+                 o_id = S.in(kcut ? cut_ids : nullptr, B * kc * 4);   // (ids beyond a node's ncut come back as given)
+    S.down(kcut ? cut_ids : nullptr, o_id, B * kc * 4);
+    int rc = S.alloc();
+    if (rc == MIPX_OK) rc = S.upload();
+    mipx::SpillArgs a;
+    a.n = n; a.nv = nv; a.kc = kcut; a.count = count;
+    a.root_l = S.at<const double>(o_rl); a.root_u = S.at<const double>(o_ru);
+    a.l = S.at<double>(o_l); a.u = S.at<double>(o_u); a.v = S.at<int8_t>(o_v);
+    a.ncut = S.at<int32_t>(o_nc); a.ids = S.at<int32_t>(o_id); a.off = S.at<int64_t>(o_off); a.rec = S.at<char>(o_rec);
+    if (rc == MIPX_OK) {
+        hipLaunchKernelGGL(mipx::spill_unpack, dim3((count + 3) / 4), dim3(256), 0, ctx->stream, a);
+        if (hipError_t e = hipGetLastError()) rc = S.err("launch", e);
+    }
+    return S.finish(rc);
 }
 
 }  // extern "C"

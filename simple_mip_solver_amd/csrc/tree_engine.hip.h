@@ -23,7 +23,7 @@ struct NodeRec {
     double key;          // queue key: dual bound (best first) or -depth (depth first)
     double dual_bound;   // bound inherited from the parent (parent's LP objective)
     double b_val;
-    int32_t slot;        // row in the device pool, -1 once released
+    int32_t slot;        // row in the device pool, -1 once released, <= -2 on the host (host spill: entry -2 - slot)
     int32_t depth;
     int32_t b_idx;       // variable branched on to create this node (-1 root)
     int32_t b_dir;       // 0 left (x <= floor), 1 right (x >= ceil)
@@ -263,9 +263,34 @@ struct StepBuf {
     int32_t *d_skeys = nullptr;                  // the samples' table entries, densely (pc_apply scans them)
     char *h_fin = nullptr;                       // pinned: [summary | table block | open entries | dead rows]
     std::vector<int32_t> budget;
+    // host spill: the batch's spilled nodes, staged pinned as [offsets (rl_n + 1) | rows | records] and unpacked
+    // into their new rows on the launch stream before the node LPs read them
+    char *h_rl = nullptr, *d_rl = nullptr;
+    int rl_n = 0;
     int B = 0;
     bool in_flight = false;
     double inflight_min = std::numeric_limits<double>::infinity();   // lowest inherited bound of the batch (exchange record)
+};
+
+// Host spill (include/mipx_spill.h): open nodes moved out of the pool into compact records in pinned host
+// memory.  One segment per spill event, freed once its last record is reloaded or dropped.
+struct SpillSeg { char *host = nullptr; int64_t bytes = 0, live = 0; };
+struct SpillLoc { int32_t seg; int32_t bytes; int64_t off; };
+struct HostSpill {
+    int64_t cap = 0;                 // max host bytes; 0: off
+    hipStream_t st = nullptr;        // count / scan / pack and the copy down, beside the steps in flight
+    double *d_root = nullptr;        // [root l | root u]
+    int32_t *d_slot = nullptr;       // one event's scratch: the victims' rows, ids, record offsets, records
+    int64_t *d_id = nullptr, *d_off = nullptr;
+    char *d_rec = nullptr;
+    size_t vict_cap = 0, rec_cap = 0, rl_cap = 0;
+    std::vector<SpillSeg> segs;
+    std::vector<int32_t> seg_free;
+    std::vector<char *> dead;        // emptied segments, freed at the next event (hipHostFree waits for the device)
+    std::vector<SpillLoc> loc;       // indexed by -2 - NodeRec::slot
+    std::vector<int32_t> loc_free;
+    int64_t bytes = 0, peak = 0, spilled = 0, reloaded = 0, on_host = 0, events = 0;
+    double spill_us = 0.0, reload_us = 0.0;
 };
 
 struct mipx_tree {
@@ -391,6 +416,8 @@ struct mipx_tree {
     uint8_t *d_is_int = nullptr;
     int64_t cut_totals[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // rounds, it/n created, it/n added, it/n removed, dropped
     double phase_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // MIPX_TREE_PROFILE=1: host-side breakdown
+    std::vector<double> root_l, root_u;   // the root's bounds (compact records store the differences)
+    HostSpill hs;
     double probe_ms[4] = {0, 0, 0, 0};  // probes phase: requests | enqueue | wait | results
 };
 
@@ -656,6 +683,216 @@ int table_replace(mipx_tree *t) {
     return MIPX_OK;
 }
 
+// ---- host spill (include/mipx_spill.h) ----
+inline bool spilled(int32_t slot) { return slot <= -2; }
+int spill_steps(const mipx_tree *t) { return t->max_batch > 1 ? 3 : 1; }
+// the rows a step launch must find free so that batch_size() grants the whole batch (see the header)
+int64_t spill_headroom(const mipx_tree *t) {
+    return (int64_t)spill_steps(t) * t->max_batch * (2 * (1 + (int64_t)t->dive) + 1);
+}
+int64_t spill_max_record(const mipx_tree *t) {
+    return mipx::spill_record_bytes(t->n, t->cuts ? t->kc : 0, t->n + t->mrows, t->cuts ? t->kc : 0);
+}
+mipx::SpillArgs spill_args(mipx_tree *t) {
+    mipx::SpillArgs a;
+    a.n = t->n; a.nv = t->n + t->mrows; a.kc = t->cuts ? t->kc : 0;
+    a.root_l = t->hs.d_root; a.root_u = t->hs.d_root + t->n;
+    a.l = t->pool_l; a.u = t->pool_u; a.v = t->pool_v; a.ncut = t->pool_ncut; a.ids = t->pool_ids;
+    return a;
+}
+
+// a spilled record leaves the store (reloaded, or its node closed unevaluated); an emptied segment is freed later
+void spill_release(mipx_tree *t, int32_t slot) {
+    HostSpill &h = t->hs;
+    const int32_t li = -2 - slot;
+    SpillSeg &g = h.segs[(size_t)h.loc[(size_t)li].seg];
+    if (--g.live == 0) {
+        h.dead.push_back(g.host);
+        h.bytes -= g.bytes;
+        g.host = nullptr;
+        g.bytes = 0;
+        h.seg_free.push_back(h.loc[(size_t)li].seg);
+    }
+    h.loc_free.push_back(li);
+    h.on_host--;
+}
+
+// Decode a spilled node's record on the host (peek_open / peek_cuts): bounds, the whole basis row, cut list.
+void spill_decode(const mipx_tree *t, int32_t slot, double *l, double *u, int8_t *v, int32_t *ids) {
+    const SpillLoc &lc = t->hs.loc[(size_t)(-2 - slot)];
+    const char *p = t->hs.segs[(size_t)lc.seg].host + lc.off;
+    const int n = t->n, nv = t->n + t->mrows;
+    int32_t nd, ncut;
+    std::memcpy(&nd, p + 8, 4);
+    std::memcpy(&ncut, p + 12, 4);
+    const int64_t o_l = 16 + mipx::spill_pad8(4 * (int64_t)nd), o_u = o_l + 8 * (int64_t)nd, o_v = o_u + 8 * (int64_t)nd;
+    if (l) std::memcpy(l, t->root_l.data(), (size_t)n * 8);
+    if (u) std::memcpy(u, t->root_u.data(), (size_t)n * 8);
+    for (int32_t q = 0; q < nd; q++) {
+        int32_t c;
+        std::memcpy(&c, p + 16 + 4 * (size_t)q, 4);
+        if (l) std::memcpy(l + c, p + o_l + 8 * (size_t)q, 8);
+        if (u) std::memcpy(u + c, p + o_u + 8 * (size_t)q, 8);
+    }
+    for (int j = 0; v && j < nv; j++) {
+        const uint8_t c = (uint8_t)p[o_v + j / 2];
+        v[j] = (int8_t)((int8_t)(j & 1 ? c : (uint8_t)(c << 4)) >> 4);
+    }
+    if (ids && ncut > 0) std::memcpy(ids, p + o_v + mipx::spill_pad8((nv + 1) / 2), (size_t)ncut * 4);
+}
+
+// One spill event: the worst-keyed resident open nodes (the queue pops them last) go to the host until
+// `target` rows are free.  Only open nodes move: the rows of the steps in flight -- their batches, and with the
+// device finish the budgets they took at launch -- are not in the queue.  Returns MIPX_ENOMEM when the records
+// would exceed the host cap (nothing moved).
+int spill_event(mipx_tree *t, int64_t target) {
+    mipx_ctx *ctx = t->ctx;
+    HostSpill &h = t->hs;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (char *q : h.dead) (void)hipHostFree(q);
+    h.dead.clear();
+    std::vector<BucketQueue::Item> items;
+    if (t->use_bq) t->bq.items(items);
+    else for (const auto &it : t->heap.h) items.push_back({it.key, it.id});
+    items.erase(std::remove_if(items.begin(), items.end(), [&](const BucketQueue::Item &it) { return t->nodes[it.id].slot < 0; }),
+                items.end());
+    const int64_t K = std::min<int64_t>(target - (int64_t)t->free_slots.size(), (int64_t)items.size());
+    if (K <= 0) return MIPX_OK;
+    auto worse = [](const BucketQueue::Item &a, const BucketQueue::Item &b) { return a.key > b.key || (a.key == b.key && a.id > b.id); };
+    std::nth_element(items.begin(), items.begin() + (K - 1), items.end(), worse);
+    items.resize((size_t)K);
+    std::sort(items.begin(), items.end(), [](const BucketQueue::Item &a, const BucketQueue::Item &b) { return a.id < b.id; });
+    if ((size_t)K > h.vict_cap) {
+        const size_t c = std::max<size_t>((size_t)K, 2 * h.vict_cap);
+        (void)hipFree(h.d_slot); (void)hipFree(h.d_id); (void)hipFree(h.d_off);
+        h.d_slot = nullptr; h.d_id = nullptr; h.d_off = nullptr; h.vict_cap = 0;
+        if (dmalloc(ctx, &h.d_slot, c) || dmalloc(ctx, &h.d_id, c) || dmalloc(ctx, &h.d_off, c + 1)) return MIPX_EHIP;
+        h.vict_cap = c;
+    }
+    std::vector<int32_t> rows((size_t)K);
+    std::vector<int64_t> ids((size_t)K), off((size_t)K + 1);
+    for (int64_t k = 0; k < K; k++) { ids[(size_t)k] = items[(size_t)k].id; rows[(size_t)k] = t->nodes[items[(size_t)k].id].slot; }
+    hipStream_t st = h.st;
+    if (t->child_recorded) HIP_TRY(ctx, hipStreamWaitEvent(st, t->ev_child, 0));   // (host finish: children rows being written)
+    HIP_TRY(ctx, hipMemcpyAsync(h.d_slot, rows.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(h.d_id, ids.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
+    mipx::SpillArgs a = spill_args(t);
+    a.count = (int)K; a.slot = h.d_slot; a.node_id = h.d_id; a.off = h.d_off;
+    const unsigned grid = (unsigned)((K + 3) / 4);
+    hipLaunchKernelGGL(mipx::spill_count, dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mipx::spill_scan, dim3(1), dim3(1024), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(off.data(), h.d_off, ((size_t)K + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    const int64_t total = off[(size_t)K];
+    if (h.bytes + total > h.cap) return MIPX_ENOMEM;
+    if ((size_t)total > h.rec_cap) {
+        (void)hipFree(h.d_rec);
+        h.d_rec = nullptr;
+        h.rec_cap = 0;
+        if (dmalloc(ctx, &h.d_rec, (size_t)total + (size_t)total / 2)) return MIPX_EHIP;
+        h.rec_cap = (size_t)total + (size_t)total / 2;
+    }
+    char *seg = nullptr;
+    HIP_TRY(ctx, hipHostMalloc((void **)&seg, (size_t)total, hipHostMallocDefault));
+    a.rec = h.d_rec;
+    hipLaunchKernelGGL(mipx::spill_pack, dim3(grid), dim3(256), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(seg, h.d_rec, (size_t)total, hipMemcpyDeviceToHost, st));
+    if (hipError_t e = hipStreamSynchronize(st)) {
+        (void)hipHostFree(seg);
+        return fail(ctx, MIPX_EHIP, "tree: host spill", e);
+    }
+    // the copy is complete: the rows are free from here on
+    int32_t si;
+    if (!h.seg_free.empty()) { si = h.seg_free.back(); h.seg_free.pop_back(); }
+    else { si = (int32_t)h.segs.size(); h.segs.emplace_back(); }
+    h.segs[(size_t)si] = {seg, total, K};
+    for (int64_t k = 0; k < K; k++) {
+        int32_t li;
+        if (!h.loc_free.empty()) { li = h.loc_free.back(); h.loc_free.pop_back(); }
+        else { li = (int32_t)h.loc.size(); h.loc.emplace_back(); }
+        h.loc[(size_t)li] = {si, (int32_t)(off[(size_t)k + 1] - off[(size_t)k]), off[(size_t)k]};
+        t->nodes[ids[(size_t)k]].slot = -2 - li;
+        t->free_slots.push_back(rows[(size_t)k]);
+    }
+    h.bytes += total;
+    h.peak = std::max(h.peak, h.bytes);
+    h.spilled += K;
+    h.on_host += K;
+    h.events++;
+    h.spill_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    return MIPX_OK;
+}
+
+// Before a launch: make sure batch_size() can grant `want` nodes (their children rows, those of the steps in
+// flight where the host finishes them, and a row per spilled node of the batch).  Below that, one event spills
+// down to a low watermark a further headroom (or an eighth of the pool) lower, so that events stay rare.
+int spill_room(mipx_tree *t, int want, int64_t inflight) {
+    const int64_t per = 2 * (1 + (int64_t)t->dive);
+    // (a traced step is finished on the host, whatever fast_ok says: its children take their rows then)
+    const int64_t need = per * want + (t->fast_ok && !t->trace ? 0 : per * inflight) + want;
+    if ((int64_t)t->free_slots.size() >= need) return MIPX_OK;
+    const int64_t target = need + std::max(spill_headroom(t), t->capacity / 8);
+    const int rc = spill_event(t, target);
+    if (rc == MIPX_ENOMEM) {   // the host store is full: stop as a full pool stops
+        t->pool_exhausted = true;
+        (void)fail(t->ctx, MIPX_ENOMEM, "tree: node pool and host spill store exhausted (search stopped; raise max_host_bytes)");
+        return MIPX_OK;
+    }
+    return rc;
+}
+
+// tree_launch: rows for the batch's spilled nodes and their records staged (the unpack is queued by
+// spill_reload_enqueue, behind the children rows of the last finished step)
+int spill_assign(mipx_tree *t, StepBuf &S) {
+    HostSpill &h = t->hs;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int B = (int)S.ids.size();
+    const size_t MB = (size_t)t->max_batch;
+    int64_t *off = (int64_t *)S.h_rl;
+    int32_t *rows = (int32_t *)(S.h_rl + (MB + 1) * 8);
+    char *rec = S.h_rl + (MB + 1) * 8 + (MB * 4 + 7) / 8 * 8;
+    int r = 0;
+    off[0] = 0;
+    for (int k = 0; k < B; k++) {
+        const int32_t sl = S.slots[(size_t)k];
+        if (!spilled(sl)) continue;
+        if (t->free_slots.empty())   // (batch_size() reserves a row per node of the batch while nodes are on the host)
+            return fail(t->ctx, MIPX_ENOMEM, "tree: no pool row for a node coming back from the host");
+        const SpillLoc &lc = h.loc[(size_t)(-2 - sl)];
+        std::memcpy(rec + off[r], h.segs[(size_t)lc.seg].host + lc.off, (size_t)lc.bytes);
+        off[r + 1] = off[r] + lc.bytes;
+        spill_release(t, sl);
+        rows[r] = t->free_slots.back();
+        t->free_slots.pop_back();
+        S.slots[(size_t)k] = rows[r];
+        r++;
+    }
+    S.rl_n = r;
+    h.reloaded += r;
+    h.reload_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    return MIPX_OK;
+}
+
+int spill_reload_enqueue(mipx_tree *t, StepBuf &S) {
+    mipx_ctx *ctx = t->ctx;
+    const int r = S.rl_n;
+    S.rl_n = 0;
+    if (r == 0) return MIPX_OK;
+    const size_t MB = (size_t)t->max_batch, o_rows = (MB + 1) * 8, o_rec = o_rows + (MB * 4 + 7) / 8 * 8;
+    const int64_t bytes = ((const int64_t *)S.h_rl)[r];
+    hipStream_t st = t->ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(S.d_rl, S.h_rl, ((size_t)r + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(S.d_rl + o_rows, S.h_rl + o_rows, (size_t)r * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(S.d_rl + o_rec, S.h_rl + o_rec, (size_t)bytes, hipMemcpyHostToDevice, st));
+    mipx::SpillArgs a = spill_args(t);
+    a.count = r; a.off = (int64_t *)S.d_rl; a.slot = (const int32_t *)(S.d_rl + o_rows); a.rec = S.d_rl + o_rec;
+    hipLaunchKernelGGL(mipx::spill_unpack, dim3((unsigned)((r + 3) / 4)), dim3(256), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
 // First half of a step: pop the batch and enqueue its node LPs + scoring (no host wait).
 int tree_launch(mipx_tree *t, StepBuf &S, int want) {
     mipx_ctx *ctx = t->ctx;
@@ -678,7 +915,8 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
         nd.slot = -1;  // (the row itself is released when the step is finished)
         if (!(nd.dual_bound < t->primal)) {
             t->closed_min = std::fmin(t->closed_min, nd.dual_bound);
-            t->free_slots.push_back(slot);
+            if (spilled(slot)) spill_release(t, slot);   // (its record is dropped, never reloaded)
+            else t->free_slots.push_back(slot);
             return;
         }
         ids.push_back(id);
@@ -702,6 +940,10 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
     }
     const int B = (int)ids.size();
     if (B == 0) return MIPX_OK;
+    if (t->hs.on_host > 0) {   // (rows for the batch's spilled nodes: before the budget below)
+        const int arc = spill_assign(t, S);
+        if (arc) return arc;
+    }
     S.B = B;
     S.in_flight = true;
     t->steps++;
@@ -751,6 +993,8 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
         // the parents' records and the pool rows the children may take: chain k, level p, direction d owns
         // budget[k][2 p + d] (the claim batch_size() left room for, handed out up front)
         const size_t per = 2 * (1 + (size_t)t->dive), need = per * (size_t)B;
+        if (t->free_slots.size() < need)   // (batch_size() left room for them: this would be an accounting bug)
+            return fail(ctx, MIPX_ENOMEM, "tree: fewer free pool rows than the batch's children budget");
         S.budget.assign(t->free_slots.end() - (std::ptrdiff_t)need, t->free_slots.end());
         t->free_slots.resize(t->free_slots.size() - need);
         double *pd = (double *)S.h_par;
@@ -770,6 +1014,10 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
     if (t->child_pending) {
         HIP_TRY(ctx, hipStreamWaitEvent(st, t->ev_child, 0));
         t->child_pending = false;
+    }
+    if (S.rl_n > 0) {   // the batch's spilled nodes back into their rows (the rows may have fed those children)
+        const int rrc = spill_reload_enqueue(t, S);
+        if (rrc) return rrc;
     }
     S.dive = t->dive;  // (register tiles and the HBM-streaming kernel alike)
     S.scored_once = false;
@@ -2084,6 +2332,8 @@ int mipx_tree_create_ex(mipx_problem *p, const int32_t *int_idx, int n_int, cons
         HIP_TRY(ctx, hipMemcpy(t->d_primal, &inf_, 8, hipMemcpyHostToDevice));
     }
     // root record in slot 0: cold start (all status codes 0 -> slack basis, sides from d_j)
+    t->root_l.assign(l, l + n);
+    t->root_u.assign(u, u + n);
     HIP_TRY(ctx, hipMemcpy(t->pool_l, l, n * 8, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(t->pool_u, u, n * 8, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemset(t->pool_v, 0, nv));
@@ -2118,6 +2368,20 @@ void mipx_tree_destroy(mipx_tree *t) {
     if (t->st3) { (void)hipStreamSynchronize(t->st3); (void)hipStreamDestroy(t->st3); }
     if (t->stf) { (void)hipStreamSynchronize(t->stf); (void)hipStreamDestroy(t->stf); }
     if (t->ev_child) (void)hipEventDestroy(t->ev_child);
+    if (t->hs.st) { (void)hipStreamSynchronize(t->hs.st); (void)hipStreamDestroy(t->hs.st); }
+    {
+        HostSpill &h = t->hs;
+        void *hp[] = {h.d_root, h.d_slot, h.d_id, h.d_off, h.d_rec};
+        for (void *q : hp)
+            if (q) (void)hipFree(q);
+        for (char *q : h.dead) (void)hipHostFree(q);
+        for (const SpillSeg &g : h.segs)
+            if (g.host) (void)hipHostFree(g.host);
+        for (StepBuf &S : t->buf) {
+            if (S.h_rl) (void)hipHostFree(S.h_rl);
+            if (S.d_rl) (void)hipFree(S.d_rl);
+        }
+    }
     if (t->h_pairs) (void)hipHostFree(t->h_pairs);
     if (t->h_pres) (void)hipHostFree(t->h_pres);
     if (t->h_tab) (void)hipHostFree(t->h_tab);
@@ -2192,6 +2456,8 @@ int mipx_tree_solve(mipx_tree *t, int64_t node_limit, double mip_gap, double max
     if (!t || frontier_batch < 1 || frontier_batch > t->max_batch)
         return fail(t ? t->ctx : nullptr, MIPX_EINVAL, "mipx_tree_solve: bad argument");
     mipx_ctx *ctx = t->ctx;
+    if (t->hs.cap > 0 && t->capacity < 2 * spill_headroom(t) + 1)
+        return fail(ctx, MIPX_EINVAL, "mipx_tree_solve: pool_capacity below the host spill headroom (see mipx_spill.h)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const auto t0 = std::chrono::steady_clock::now();
     const double inf = std::numeric_limits<double>::infinity();
@@ -2252,7 +2518,10 @@ int mipx_tree_solve(mipx_tree *t, int64_t node_limit, double mip_gap, double max
         // a single node's children the search stops (status 4, stats.pool_exhausted).
         const int64_t per = 2 * (1 + (int64_t)t->dive);
         // (device finish: the steps in flight took their rows out of the free list when they were launched)
-        const int64_t room = ((int64_t)t->free_slots.size() - (t->fast_ok ? 0 : per * inflight)) / per;
+        const int64_t avail = (int64_t)t->free_slots.size() - (t->fast_ok ? 0 : per * inflight);
+        // host spill: a node of the batch may come back from the host and need a row of its own besides its
+        // children's (while any node is on the host, whether or not the spill is still on)
+        const int64_t room = avail / (t->hs.on_host > 0 ? per + 1 : per);
         if (room < want) {
             want = room > 0 ? room : 0;
             if (want == 0 && inflight == 0) {
@@ -2269,6 +2538,11 @@ int mipx_tree_solve(mipx_tree *t, int64_t node_limit, double mip_gap, double max
         while (nfl < NBUF && !tree_queue_empty(t)) {
             const int64_t fl = inflight_nodes();
             if (stop_now(fl)) break;
+            if (t->hs.cap > 0) {   // host spill: rows for a whole batch before batch_size() counts them
+                const int src = spill_room(t, frontier_batch, fl);
+                if (src) return bail(src);
+                if (t->pool_exhausted) break;
+            }
             const int want = batch_size(fl);
             if (nfl > 0 && want <= 0) break;
             StepBuf &N = t->buf[next];
@@ -2363,9 +2637,10 @@ int mipx_tree_reanchor(mipx_tree *t, int64_t max_nodes) {
     std::vector<int64_t> order;
     tree_queue_ids(t, order);
     if (t->cuts) {   // an anchor is a tableau of the shared rows: only nodes that carry no cut row get one
-        std::stable_partition(order.begin(), order.end(), [&](int64_t id) { return t->nodes[id].ncut == 0; });
+        auto plain_node = [&](int64_t id) { return t->nodes[id].ncut == 0; };
+        std::stable_partition(order.begin(), order.end(), plain_node);
         int64_t plain = 0;
-        for (int64_t id : order) plain += t->nodes[id].ncut == 0;
+        for (int64_t id : order) plain += plain_node(id);
         max_nodes = std::min<int64_t>(max_nodes, plain);
     }
     const int64_t K = std::min<int64_t>(max_nodes, (int64_t)order.size());
@@ -2387,9 +2662,51 @@ int mipx_tree_reanchor(mipx_tree *t, int64_t max_nodes) {
     }
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(d_sl, sl.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
+    // host spill: spilled nodes among the K are decoded into a scratch block shaped like the pool (row k for
+    // the k-th node), the resident ones copied beside them -- every one of the K gets the anchor it would get
+    // in a pool that never filled
+    const double *src_l = t->pool_l, *src_u = t->pool_u;
+    const int8_t *src_v = t->pool_v;
+    double *sc_l = nullptr, *sc_u = nullptr;
+    int8_t *sc_v = nullptr;
+    char *sc_rec = nullptr;
+    std::vector<int32_t> pos, idn;
+    std::vector<int64_t> roff(1, 0);
+    std::vector<char> recs;
+    for (int64_t k = 0; k < K; k++) {
+        if (!spilled(sl[(size_t)k])) continue;
+        const SpillLoc &lc = t->hs.loc[(size_t)(-2 - sl[(size_t)k])];
+        const char *src = t->hs.segs[(size_t)lc.seg].host + lc.off;
+        recs.insert(recs.end(), src, src + lc.bytes);
+        roff.push_back((int64_t)recs.size());
+        pos.push_back((int32_t)k);
+    }
+    if (!pos.empty()) {
+        const size_t nvs = n + (size_t)t->mrows, R = pos.size(), o_pos = (R + 1) * 8, o_rec = o_pos + (R * 4 + 7) / 8 * 8;
+        HIP_TRY(ctx, hipMalloc((void **)&sc_l, (size_t)K * n * 8));
+        HIP_TRY(ctx, hipMalloc((void **)&sc_u, (size_t)K * n * 8));
+        HIP_TRY(ctx, hipMalloc((void **)&sc_v, (size_t)K * nvs));
+        HIP_TRY(ctx, hipMalloc((void **)&sc_rec, o_rec + recs.size()));
+        mipx::SpillArgs a = spill_args(t);
+        a.kc = 0;   // (the K are plain nodes or no cut rounds run: only bounds and basis codes are needed)
+        a.l = sc_l; a.u = sc_u; a.v = sc_v; a.ncut = nullptr; a.ids = nullptr;
+        a.count = (int)K; a.slot = d_sl;
+        hipLaunchKernelGGL(mipx::spill_gather_rows, dim3((unsigned)K), dim3(256), 0, st, a, (const double *)t->pool_l,
+                           (const double *)t->pool_u, (const int8_t *)t->pool_v);
+        HIP_TRY(ctx, hipMemcpyAsync(sc_rec, roff.data(), (R + 1) * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(sc_rec + o_pos, pos.data(), R * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(sc_rec + o_rec, recs.data(), recs.size(), hipMemcpyHostToDevice, st));
+        a.count = (int)R; a.off = (int64_t *)sc_rec; a.slot = (const int32_t *)(sc_rec + o_pos); a.rec = sc_rec + o_rec;
+        hipLaunchKernelGGL(mipx::spill_unpack, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a);
+        HIP_TRY(ctx, hipGetLastError());
+        idn.resize((size_t)K);
+        for (int64_t k = 0; k < K; k++) idn[(size_t)k] = (int32_t)k;
+        HIP_TRY(ctx, hipMemcpyAsync(d_sl, idn.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+        src_l = sc_l; src_u = sc_u; src_v = sc_v;
+    }
     // refactor-only solves of the K nodes (from the anchors they have now), every final tableau dumped
     mipx::LpArgs a = problem_args(t->prob);
-    a.l = t->pool_l; a.u = t->pool_u; a.vstat_in = t->pool_v; a.slot = d_sl;
+    a.l = src_l; a.u = src_u; a.vstat_in = src_v; a.slot = d_sl;
     double *gl = nullptr, *gu = nullptr;
     int8_t *gv = nullptr;
     if (t->cuts) {   // (the pool's basis rows are n + mrows wide: dense copies over the shared rows)
@@ -2398,7 +2715,7 @@ int mipx_tree_reanchor(mipx_tree *t, int64_t max_nodes) {
         HIP_TRY(ctx, hipMalloc((void **)&gv, (size_t)K * (n + m)));
         mipx::PlainGatherArgs ga;
         ga.n = (int)n; ga.m = (int)m; ga.nvs_pool = t->n + t->mrows; ga.count = (int)K; ga.slot = d_sl;
-        ga.pool_l = t->pool_l; ga.pool_u = t->pool_u; ga.pool_v = t->pool_v; ga.l = gl; ga.u = gu; ga.v = gv;
+        ga.pool_l = src_l; ga.pool_u = src_u; ga.pool_v = src_v; ga.l = gl; ga.u = gu; ga.v = gv;
         hipLaunchKernelGGL(mipx::gather_plain_nodes, dim3((unsigned)K), dim3(256), 0, st, ga);
         a.l = gl; a.u = gu; a.vstat_in = gv; a.slot = nullptr;
     }
@@ -2409,6 +2726,7 @@ int mipx_tree_reanchor(mipx_tree *t, int64_t max_nodes) {
     if (rc == MIPX_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(ctx, MIPX_EHIP, "mipx_tree_reanchor: launch failed");
     (void)hipFree(d_sl);
     if (gl) { (void)hipFree(gl); (void)hipFree(gu); (void)hipFree(gv); }
+    if (sc_l) { (void)hipFree(sc_l); (void)hipFree(sc_u); (void)hipFree(sc_v); (void)hipFree(sc_rec); }
     if (rc != MIPX_OK) { (void)hipFree(nT); (void)hipFree(nvec); (void)hipFree(nidx); return rc; }
     if (t->atab_T) { (void)hipFree(t->atab_T); (void)hipFree(t->atab_vec); (void)hipFree(t->atab_idx); }
     t->atab_T = nT; t->atab_vec = nvec; t->atab_idx = nidx; t->atab_count = K;
@@ -2484,6 +2802,8 @@ int mipx_exchange_decide(int world, int n, const double *records, double mip_gap
 int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps) {
     if (!t || (c && every_steps < 1)) return MIPX_EINVAL;
     if (c && c->ctx != t->ctx) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: communicator of another context");
+    if (c && (t->hs.cap > 0 || t->hs.on_host > 0))
+        return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the host spill (mipx_tree_set_host_spill)");
     t->comm = c;
     t->x_every = c ? every_steps : 0;
     if (!c) return MIPX_OK;
@@ -2626,11 +2946,17 @@ int64_t mipx_tree_peek_open(mipx_tree *t, int64_t max_nodes, double *l, double *
     tree_queue_ids(t, order);
     for (size_t pos = 0; pos < order.size() && k < max_nodes; pos++, k++) {
         const NodeRec &nd = t->nodes[order[pos]];
+        if (dual_bound) dual_bound[k] = nd.dual_bound;
+        if (spilled(nd.slot)) {   // (decoded from its compact record)
+            std::vector<int8_t> row(vstat ? nvs : 0);
+            spill_decode(t, nd.slot, l ? l + k * n : nullptr, u ? u + k * n : nullptr, vstat ? row.data() : nullptr, nullptr);
+            if (vstat) std::memcpy(vstat + k * nv, row.data(), nv);
+            continue;
+        }
         const size_t s = (size_t)nd.slot;
         if (l && hipMemcpy(l + k * n, t->pool_l + s * n, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return MIPX_EHIP;
         if (u && hipMemcpy(u + k * n, t->pool_u + s * n, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return MIPX_EHIP;
         if (vstat && hipMemcpy(vstat + k * nv, t->pool_v + s * nvs, nv, hipMemcpyDeviceToHost) != hipSuccess) return MIPX_EHIP;
-        if (dual_bound) dual_bound[k] = nd.dual_bound;
     }
     return k;
 }
@@ -2676,7 +3002,9 @@ int mipx_tree_keep_shard(mipx_tree *t, int rank, int world) {
         if ((int)(pos % (size_t)world) == rank) {
             tree_push(t, id);
         } else {
-            t->free_slots.push_back(t->nodes[id].slot);
+            const int32_t sl = t->nodes[id].slot;
+            if (spilled(sl)) spill_release(t, sl);
+            else t->free_slots.push_back(sl);
             t->nodes[id].slot = -1;
         }
     }
@@ -2708,7 +3036,13 @@ int64_t mipx_tree_peek_cuts(mipx_tree *t, int64_t max_nodes, int64_t *node_id, i
         const size_t s = (size_t)nd.slot;
         if (node_id) node_id[k] = order[pos];
         if (ncut) ncut[k] = t->cuts ? nd.ncut : 0;
-        if (t->cuts && K > 0) {
+        if (t->cuts && K > 0 && spilled(nd.slot)) {   // (decoded from its compact record)
+            std::vector<int8_t> row(nvs);
+            std::vector<int32_t> idl(K, 0);
+            spill_decode(t, nd.slot, nullptr, nullptr, row.data(), idl.data());
+            if (cut_ids) std::memcpy(cut_ids + k * K, idl.data(), K * 4);
+            if (cut_vstat) std::memcpy(cut_vstat + k * K, row.data() + n + m, K);
+        } else if (t->cuts && K > 0) {
             if (cut_ids && hipMemcpy(cut_ids + k * K, t->pool_ids + s * K, K * 4, hipMemcpyDeviceToHost) != hipSuccess) return MIPX_EHIP;
             if (cut_vstat && hipMemcpy(cut_vstat + k * K, t->pool_v + s * nvs + n + m, K, hipMemcpyDeviceToHost) != hipSuccess) return MIPX_EHIP;
         }
@@ -2742,6 +3076,42 @@ int64_t mipx_tree_trace(mipx_tree *t, int64_t capacity, int64_t *node_id, int32_
         if (objective) objective[i] = t->tr_obj[i];
     }
     return (int64_t)t->tr_id.size();
+}
+
+int mipx_tree_set_host_spill(mipx_tree *t, int64_t max_host_bytes) {
+    if (!t) return MIPX_EINVAL;
+    mipx_ctx *ctx = t->ctx;
+    if (max_host_bytes < 0) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_host_spill: negative byte cap");
+    if (max_host_bytes == 0) { t->hs.cap = 0; return MIPX_OK; }   // (nodes already on the host still come back)
+    if (t->comm) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_host_spill: not with a communicator");
+    if (t->capacity < 2 * spill_headroom(t) + 1)
+        return fail(ctx, MIPX_EINVAL, "mipx_tree_set_host_spill: pool_capacity below the minimum (2 x headroom + 1, mipx_spill.h)");
+    HostSpill &h = t->hs;
+    if (!h.st) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)t->n, MB = (size_t)t->max_batch;
+        HIP_TRY(ctx, hipStreamCreateWithFlags(&h.st, hipStreamNonBlocking));
+        int rc = dmalloc(ctx, &h.d_root, 2 * n);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpy(h.d_root, t->root_l.data(), n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(h.d_root + n, t->root_u.data(), n * 8, hipMemcpyHostToDevice));
+        // reload staging per step buffer: [offsets | rows | max_batch records of the largest size]
+        h.rl_cap = (MB + 1) * 8 + (MB * 4 + 7) / 8 * 8 + MB * (size_t)spill_max_record(t);
+        for (StepBuf &S : t->buf) {
+            HIP_TRY(ctx, hipHostMalloc((void **)&S.h_rl, h.rl_cap, hipHostMallocDefault));
+            if ((rc = dmalloc(ctx, &S.d_rl, h.rl_cap))) return rc;
+        }
+    }
+    h.cap = max_host_bytes;
+    return MIPX_OK;
+}
+
+int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
+    if (!t || !out) return MIPX_EINVAL;
+    const HostSpill &h = t->hs;
+    out[0] = h.spilled; out[1] = h.reloaded; out[2] = h.on_host; out[3] = h.bytes; out[4] = h.peak; out[5] = h.events;
+    out[6] = (int64_t)h.spill_us; out[7] = (int64_t)h.reload_us;
+    return MIPX_OK;
 }
 
 }  // extern "C"
