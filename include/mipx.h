@@ -465,7 +465,8 @@ int mipx_comm_barrier(mipx_comm *c);
  *     max_seconds (they count per rank), or every rank done with its max_steps (a per-rank quota: a
  *     rank that has done its steps waits in the exchange while the others finish theirs);
  *   - migration: a rank that cannot fill a batch gets half the surplus of the fullest rank (node
- *     records move by ncclSend / ncclRecv; not with cut rounds).
+ *     records move by ncclSend / ncclRecv; with cut rounds only when every rank has cut migration on,
+ *     mipx_cutmig.h, and then with their cut rows).
  * A rank without open nodes blocks in the exchange until work or the end arrives.  After the solve
  * mipx_tree_get_stats / mipx_tree_solution report the GLOBAL incumbent on every rank;
  * mipx_tree_global_stats adds the summed counters.
@@ -477,14 +478,18 @@ int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps);
  * [2] open nodes (queued + in flight), [3] stop flag, [4..7] evaluated / LPs / probes / pivots since
  * sharding, [8] 1 if the rank holds a solution for [0], [9] exchange number, [10] its frontier batch,
  * [11] pool rows it can take from a donor, [12] the lowest bound among its nodes in flight (inf: none;
- * [1] includes it: a shard's dual bound covers queued, in-flight and closed nodes),
+ * [1] includes it: a shard's dual bound covers queued, in-flight and closed nodes), [13] rows its cut
+ * migration region can still take, [14] cut rows per node (kc) if cut migration is on, else 0, [15] 1 if
+ * the tree runs cut rounds ([13..15] are 0 without cut rounds; mipx_cutmig.h),
  * [16..16+n) the solution, then 4 n pseudo-cost samples (sum_l, sum_r, times_l, times_r).
  * [3] stop flag: 1 a limit that ends the search, 2 the rank's step quota is done, 3 the rank failed
  * (it is returning an error: every other rank stops and returns MIPX_EPEER).
  * reason: 0 go on, 1 no open node anywhere, 2 a rank's limit, 3 global gap <= mip_gap, 4 every rank has
  * done its steps or run dry, 5 a rank failed.
  * moves: n_moves triples (from rank, to rank, node records), in the order they are carried out; a move
- * never exceeds the room [11] its receiver reported. */
+ * never exceeds the room [11] its receiver reported; a rank receives at most one move per decision.  If any
+ * record has [15] set, nodes move only when every record has [15] set and the same [14] > 0.
+ * allow_migration = 0: no moves. */
 typedef struct mipx_exchange_decision {
     double primal, dual, gap;
     int64_t sums[4], open_nodes;
@@ -497,7 +502,8 @@ int mipx_exchange_decide(int world, int n, const double *records, double mip_gap
 /* Test hook: up to `amount` open nodes travel from this rank to itself through the communicator's
  * point-to-point path (pack kernel -> ncclSend + ncclRecv to the own rank in one ncclGroupStart / End ->
  * unpack kernel; custom transport: a device copy), i.e. what a migration does between two ranks.
- * Returns the number of records moved.  Not with cut rounds, not with a step in flight. */
+ * Returns the number of records moved.  With cut rounds only when cut migration is on (mipx_cutmig.h): the
+ * cut rows travel in the message and land in the tree's own migration region.  Not with a step in flight. */
 int64_t mipx_tree_migrate_self(mipx_tree *t, int64_t amount);
 /* Test hook: the record this rank would post right now (mipx_exchange_record_len(n) doubles; callable
  * from a step hook, i.e. with steps in flight). */
@@ -523,5 +529,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #endif
 
 #include "mipx_spill.h"   /* host spill of the frontier engine and its compact node records */
+#include "mipx_cutmig.h"  /* migration of nodes with their cut rows in cut-round mode */
 
 #endif /* MIPX_H */

@@ -205,6 +205,18 @@ SPILL_SYMBOLS = list(_SPILL_SIGNATURES)
 SPILL_STATS_KEYS = ('spilled', 'reloaded', 'on_host', 'host_bytes', 'peak_host_bytes', 'events', 'spill_ms',
                     'reload_ms')
 
+# ... and those of include/mipx_cutmig.h (node migration with cut rows), which mipx.h includes
+# (tests/test_cut_migration_cpu.py checks them against that header)
+_CUTMIG_SIGNATURES = {
+    'mipx_tree_set_cut_migration': (_i, [_vp, _i64]),
+    'mipx_tree_cut_rows': (_i, [_vp, _i64, _vp, _vp, _vp]),
+    'mipx_tree_cut_migration_stats': (_i, [_vp, _vp]),
+}
+CUTMIG_SYMBOLS = list(_CUTMIG_SIGNATURES)
+CUTMIG_STATS_KEYS = ('nodes_sent_with_cuts', 'cut_rows_sent', 'cut_rows_received', 'region_rows_used')
+# rows of the migration region that cut_migration=True / set_cut_migration(True) reserve
+DEFAULT_CUT_MIGRATION_ROWS = 1 << 16
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -217,7 +229,8 @@ def lib():
             f'(run `make -C {os.path.dirname(LIB_PATH)}` or __graft_entry__.build()). '
             'simple_mip_solver_amd has no CPU fallback.')
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_SPILL_SIGNATURES.items()):
+    for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_SPILL_SIGNATURES.items()) +
+                                      list(_CUTMIG_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -871,6 +884,28 @@ class Tree:
         d['spill_ms'] /= 1000.0
         d['reload_ms'] /= 1000.0
         return d
+
+    def set_cut_migration(self, rows):
+        """Reserve the top `rows` rows of the cut store for the cut rows of nodes received from other ranks, so
+        that open nodes can migrate in cut-round mode (mipx_tree_set_cut_migration, include/mipx_cutmig.h;
+        True: DEFAULT_CUT_MIGRATION_ROWS, 0 / False: off)."""
+        rows = DEFAULT_CUT_MIGRATION_ROWS if rows is True else int(rows)
+        self.problem.ctx.check(lib().mipx_tree_set_cut_migration(self._h, rows), 'mipx_tree_set_cut_migration')
+
+    def cut_rows(self, ids):
+        """(pi, pi0) of the cut store rows `ids`, own or migrated (mipx_tree_cut_rows)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        pi = np.zeros((len(ids), self.problem.n)); pi0 = np.zeros(len(ids))
+        self.problem.ctx.check(lib().mipx_tree_cut_rows(self._h, len(ids), _ptr(ids), _ptr(pi), _ptr(pi0)),
+                               'mipx_tree_cut_rows')
+        return pi, pi0
+
+    def cut_migration_stats(self):
+        """dict(nodes_sent_with_cuts, cut_rows_sent, cut_rows_received, region_rows_used)
+        (mipx_tree_cut_migration_stats)."""
+        out = np.zeros(4, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_cut_migration_stats(self._h, _ptr(out)), 'mipx_tree_cut_migration_stats')
+        return dict(zip(CUTMIG_STATS_KEYS, (int(v) for v in out)))
 
     def peek_open(self, max_nodes):
         """(l, u, vstat, dual_bound) of up to max_nodes open nodes, without removing them."""

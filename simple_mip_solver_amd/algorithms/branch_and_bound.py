@@ -124,7 +124,7 @@ class BranchAndBound(BaseAlgorithm):
     def __init__(self, model, Node=BaseNode, node_queue=None, node_limit=INF, mip_gap=.0001,
                  logging=False, max_run_time=INF, initial_primal_bound=INF, frontier_batch=None,
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
-                 host_spill=None, **kwargs):
+                 host_spill=None, cut_migration=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -141,7 +141,13 @@ class BranchAndBound(BaseAlgorithm):
         calls solve(): after a replicated ramp-up the open nodes are sharded over the ranks, which
         exchange incumbent (value and solution), bounds, pseudo costs and node records every
         `exchange_every` steps over RCCL; every rank ends with the same status, objective_value and
-        solution; evaluated_nodes is the total over all ranks.
+        solution; evaluated_nodes is the total over all ranks.  With gomory_cuts=True open nodes move
+        between ranks only with cut_migration.
+        cut_migration (extension; needs comm and gomory_cuts=True; default None = off): open nodes migrate
+        between ranks in cut-round mode too, carrying their cut rows (include/mipx_cutmig.h).  The top rows
+        of every rank's cut store are reserved for the rows it receives: True reserves 2**16 rows, an int
+        that many (below the store's 2**20 rows); the rank's own cuts stop that much sooner.  Every rank
+        must pass the same setting, or no node moves.  Counters: `cut_migration_stats`.
         anchor / dive (default: on for frontier_batch > 1, register-tile shapes): warm starts
         refactor from the root's optimal tableau instead of the slack basis; the workgroup that
         solved a node also solves one child on the tableau it holds (same optimum, another node
@@ -181,6 +187,13 @@ class BranchAndBound(BaseAlgorithm):
             'host_spill is None, True or a positive number of bytes'
         assert host_spill is None or frontier_batch is not None, 'host_spill needs frontier_batch'
         assert host_spill is None or comm is None, 'host_spill cannot be combined with comm'
+        assert cut_migration is None or cut_migration is True or (
+            isinstance(cut_migration, int) and not isinstance(cut_migration, bool) and cut_migration > 0), \
+            'cut_migration is None, True or a positive number of rows'
+        assert cut_migration is None or comm is not None, 'cut_migration needs comm'
+        assert cut_migration is None or kwargs.get('gomory_cuts', True) is True, 'cut_migration needs gomory_cuts=True'
+        self._cut_migration = cut_migration
+        self.cut_migration_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -347,6 +360,8 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_dive(self._dive)
             if self._host_spill:
                 self._native.set_host_spill(self._host_spill)
+            if self._cut_migration:
+                self._native.set_cut_migration(self._cut_migration)
         st = None
         if self._comm is not None and not self._sharded:
             from simple_mip_solver_amd.parallel import shard_and_attach
@@ -367,6 +382,8 @@ class BranchAndBound(BaseAlgorithm):
         self._native_stats = st
         if self._host_spill:
             self.spill_stats = self._native.spill_stats()
+        if self._cut_migration:
+            self.cut_migration_stats = self._native.cut_migration_stats()
         if st['pool_exhausted']:
             import warnings
             if self._host_spill:

@@ -15,9 +15,11 @@
 #include <limits>
 #include <memory>
 #include <queue>
+#include <unordered_map>
 
 #include "tree_kernels.hip.h"
 #include "finish_kernels.hip.h"
+#include "cutmig_kernels.hip.h"
 
 struct NodeRec {
     double key;          // queue key: dual bound (best first) or -depth (depth first)
@@ -418,6 +420,10 @@ struct mipx_tree {
     double phase_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // MIPX_TREE_PROFILE=1: host-side breakdown
     std::vector<double> root_l, root_u;   // the root's bounds (compact records store the differences)
     HostSpill hs;
+    // cut migration (mipx_tree_set_cut_migration): the top cm_rows rows of the cut store take the cut rows
+    // of nodes received from other ranks, filled in order by the migration code (host-side fill level)
+    int64_t cm_rows = 0, cm_used = 0;
+    int64_t cm_nodes_sent = 0, cm_rows_sent = 0, cm_rows_received = 0;
     double probe_ms[4] = {0, 0, 0, 0};  // probes phase: requests | enqueue | wait | results
 };
 
@@ -1164,7 +1170,7 @@ int tree_cut_rounds(mipx_tree *t, StepBuf &S) {
         aa.slab_pi = S.slab_pi; aa.slab_pi0 = S.slab_pi0; aa.pool_list = S.pool_list;
         aa.vstat = S.d_vout; aa.ncut = S.w_ncut; aa.ids = S.w_ids; aa.state = S.cs_state;
         aa.store_pi = t->store_pi; aa.store_pi0 = t->store_pi0; aa.store_count = t->store_count;
-        aa.store_cap = (int)t->store_cap;
+        aa.store_cap = (int)(t->store_cap - t->cm_rows);   // (the migration region is not K3's)
         aa.resolve = S.cs_resolve; aa.counters = S.cs_counters;
         hipLaunchKernelGGL(mipx::cut_round_apply, dim3(B), dim3(256), 0, st, aa);
         HIP_TRY(ctx, hipGetLastError());
@@ -1758,6 +1764,9 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
 // ---- the exchange between the ranks of one search (mipx_tree_set_comm) --------------------------------
 constexpr int kRecHead = 16;         // doubles in front of a record's solution and pseudo-cost samples
 constexpr int64_t kMaxMigrate = 4096;  // node records per donation
+// cut rows per donation (cut migration): the table of one message is at most 2^14 rows of n + 1 f64,
+// 33.7 MB at n = 256 (mipx_cutmig.h)
+constexpr int64_t kMaxMigrateCuts = (int64_t)1 << 14;
 
 size_t x_rec_len(const mipx_tree *t) { return (size_t)kRecHead + 5 * (size_t)t->n; }
 
@@ -1794,6 +1803,11 @@ void x_fill_record(mipx_tree *t) {
         r[11] = (double)(room > 0 ? room : 0);
     }
     r[12] = inflight_min;
+    if (t->cuts) {   // (zero in a tree without cut rounds)
+        r[13] = t->cm_rows > 0 ? (double)(t->cm_rows - t->cm_used) : 0.0;   // migration region rows still free
+        r[14] = t->cm_rows > 0 ? (double)t->kc : 0.0;
+        r[15] = 1.0;
+    }
     if (t->have_x) std::memcpy(r.data() + kRecHead, t->best_x.data(), n * 8);
     std::memcpy(r.data() + kRecHead + n, t->pc_own.data(), 4 * n * 8);
 }
@@ -1802,14 +1816,51 @@ void x_fill_record(mipx_tree *t) {
 // every rank).  The donor gives every second of its best 2 * amount open nodes, so that both keep
 // good ones; fewer if it has consumed them since it posted (the message has the planned size, a
 // count in front says how many records are real).
-struct MigLayout { size_t rowbytes, meta_off, bytes; };
-MigLayout mig_layout(const mipx_tree *t, int64_t amount) {
+//
+// With cut rounds (cut migration on at both ends) the message also carries each record's cut list as refs
+// into a table of the cut rows themselves, every store id once; ctab, the table's planned rows, is computed
+// by both ends from the same records (mig_table_rows).  Layout:
+//   [amount rows: l, u (n f64 each), basis codes (nvs int8, padded to 8)]
+//   cut mode: [amount x (1 + kc) int32: ncut, refs into the table, list order] (padded to 8)
+//             [ctab x n f64: pi] [ctab f64: pi0]
+//   [meta f64: count, then 5 per record (dual bound, b_val, depth, b_idx, b_dir); cut mode: 6 (+ ncut) and,
+//    after the records, the table rows used]
+// and behind the message the scratch of the kernels: the pool rows (amount int32), in cut mode the store ids
+// of the table rows (ctab int32) and a flag.
+struct MigLayout {
+    size_t rowbytes, meta_off, bytes;
+    size_t refs_off = 0, tab_off = 0, nmeta = 0, scratch = 0;
+    int64_t ctab = 0;
+    int kc = 0;   // > 0: cut mode
+};
+size_t pad8(size_t b) { return (b + 7) / 8 * 8; }
+MigLayout mig_layout(const mipx_tree *t, int64_t amount, int64_t ctab = 0) {
     const size_t n = (size_t)t->n, nvs = n + (size_t)t->mrows;
     MigLayout L;
     L.rowbytes = 16 * n + (nvs + 7) / 8 * 8;
-    L.meta_off = (size_t)amount * L.rowbytes;
-    L.bytes = L.meta_off + (1 + 5 * (size_t)amount) * 8;
+    if (!t->cuts) {
+        L.meta_off = (size_t)amount * L.rowbytes;
+        L.nmeta = 1 + 5 * (size_t)amount;
+        L.bytes = L.meta_off + L.nmeta * 8;
+        L.scratch = (size_t)amount * 4;
+        return L;
+    }
+    L.kc = t->kc;
+    L.ctab = ctab;
+    L.refs_off = (size_t)amount * L.rowbytes;
+    L.tab_off = L.refs_off + pad8((size_t)amount * (1 + (size_t)L.kc) * 4);
+    L.meta_off = L.tab_off + (size_t)ctab * (n + 1) * 8;
+    L.nmeta = 1 + 6 * (size_t)amount + 1;
+    L.bytes = L.meta_off + L.nmeta * 8;
+    L.scratch = pad8((size_t)amount * 4) + pad8((size_t)ctab * 4) + 8;
     return L;
+}
+// the table rows of a donation: what the receiver's region can still take ([13] of its record), at most
+// kMaxMigrateCuts, and never more than the records can refer to
+int64_t mig_table_rows(double region_free, int64_t amount, int kc) {
+    int64_t c = std::min<int64_t>((int64_t)region_free, kMaxMigrateCuts);
+    c = std::min<int64_t>(c, amount * (int64_t)kc);
+    return c > 0 ? c : 0;
 }
 mipx::PackArgs mig_args(mipx_tree *t, const MigLayout &L, char *msg, int32_t *d_slots) {
     mipx::PackArgs pa;
@@ -1902,25 +1953,203 @@ int mig_unpack(mipx_tree *t, const MigLayout &L, char *msg, int32_t *d_slots, in
     return MIPX_OK;
 }
 
-int x_migrate(mipx_tree *t, int from, int to, int64_t amount) {
+// Cut mode (mipx_tree_set_cut_migration).  scratch: the kernels' scratch behind the message (MigLayout).
+int32_t *mig_src(int32_t *scratch, int64_t amount) { return (int32_t *)((char *)scratch + pad8((size_t)amount * 4)); }
+int32_t *mig_bad(const MigLayout &L, int32_t *scratch, int64_t amount) {
+    return (int32_t *)((char *)mig_src(scratch, amount) + pad8((size_t)L.ctab * 4));
+}
+
+// donor half, cut mode: the candidates are chosen as in mig_pack; their cut lists come to the host, and in
+// candidate order a node travels if the distinct store ids it adds to the table still fit in L.ctab rows
+// (a node without cut rows always does), else it is kept and goes back into the queue
+int mig_pack_cuts(mipx_tree *t, const MigLayout &L, char *msg, int32_t *scratch, int64_t amount,
+                  std::vector<int32_t> &slots, int64_t *count, int64_t *table_rows) {
+    mipx_ctx *ctx = t->ctx;
+    const int K = L.kc;
+    const size_t W = 1 + (size_t)K;
+    std::vector<double> meta(L.nmeta, 0.0);
+    if (t->child_recorded) HIP_TRY(ctx, hipStreamWaitEvent(t->st2, t->ev_child, 0));
+    const int64_t have = tree_open_count(t);
+    const int64_t give = std::max<int64_t>(0, std::min<int64_t>(amount, (have - t->x_batch) / 2));
+    std::vector<int64_t> ids, cand;
+    if (t->use_bq) {
+        t->popped.clear();
+        t->bq.pop_batch((size_t)(2 * give), t->popped);
+        for (const auto &it : t->popped) ids.push_back(it.id);
+    } else {
+        for (int64_t k = 0; k < 2 * give && !t->heap.empty(); k++) ids.push_back(t->heap.pop());
+    }
+    for (size_t k = 0; k < ids.size(); k++) {
+        if (t->search != 0) t->is_open[ids[k]] = 0;
+        if ((k & 1) == 0 || (int64_t)cand.size() >= give) tree_push(t, ids[k]);   // kept
+        else cand.push_back(ids[k]);
+    }
+    // the candidates' cut lists, staged in the message's refs section
+    int32_t *d_lists = (int32_t *)(msg + L.refs_off);
+    std::vector<int32_t> lists(cand.size() * W);
+    if (!cand.empty()) {
+        for (int64_t id : cand) slots.push_back(t->nodes[id].slot);
+        HIP_TRY(ctx, hipMemcpyAsync(scratch, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, t->st2));
+        mipx::CutMigArgs ca;
+        ca.kc = K; ca.count = (int)cand.size(); ca.slot = scratch; ca.pool_ncut = t->pool_ncut; ca.pool_ids = t->pool_ids;
+        ca.lists = d_lists;
+        hipLaunchKernelGGL(mipx::cutmig_lists, dim3((unsigned)((cand.size() + 3) / 4)), dim3(256), 0, t->st2, ca);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(lists.data(), d_lists, lists.size() * 4, hipMemcpyDeviceToHost, t->st2));
+        HIP_TRY(ctx, hipStreamSynchronize(t->st2));
+        slots.clear();
+    }
+    std::unordered_map<int32_t, int32_t> ref;   // store id -> table row
+    std::vector<int32_t> src, refs;             // table rows' store ids; the records' [ncut, refs]
+    int64_t cnt = 0, with_cuts = 0;
+    for (size_t i = 0; i < cand.size(); i++) {
+        const int32_t *li = lists.data() + i * W;
+        const int nc = li[0];
+        if (nc < 0 || nc > K) return fail(ctx, MIPX_EHIP, "tree: corrupt cut list in the node pool");
+        int64_t fresh = 0;
+        for (int j = 0; j < nc; j++) {
+            if (li[1 + j] < 0 || li[1 + j] >= t->store_cap) return fail(ctx, MIPX_EHIP, "tree: corrupt cut list in the node pool");
+            bool seen = ref.count(li[1 + j]) > 0;
+            for (int q = 0; q < j && !seen; q++) seen = li[1 + q] == li[1 + j];
+            fresh += seen ? 0 : 1;
+        }
+        if ((int64_t)src.size() + fresh > L.ctab) { tree_push(t, cand[i]); continue; }   // kept: its rows do not fit
+        NodeRec &nd = t->nodes[cand[i]];
+        refs.push_back(nc);
+        for (int j = 0; j < nc; j++) {
+            auto it = ref.find(li[1 + j]);
+            if (it == ref.end()) {
+                it = ref.emplace(li[1 + j], (int32_t)src.size()).first;
+                src.push_back(li[1 + j]);
+            }
+            refs.push_back(it->second);
+        }
+        for (int j = nc; j < K; j++) refs.push_back(0);
+        double *mrec = meta.data() + 1 + 6 * cnt;
+        mrec[0] = nd.dual_bound; mrec[1] = nd.b_val; mrec[2] = (double)nd.depth;
+        mrec[3] = (double)nd.b_idx; mrec[4] = (double)nd.b_dir; mrec[5] = (double)nc;
+        slots.push_back(nd.slot);
+        nd.slot = -1;
+        with_cuts += nc > 0;
+        cnt++;
+    }
+    meta[0] = (double)cnt;
+    meta[L.nmeta - 1] = (double)src.size();
+    if (cnt > 0) {
+        mipx::PackArgs pa = mig_args(t, L, msg, scratch);
+        HIP_TRY(ctx, hipMemcpyAsync(scratch, slots.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, t->st2));
+        pa.count = (int)cnt;
+        hipLaunchKernelGGL(mipx::pack_nodes, dim3((unsigned)cnt), dim3(256), 0, t->st2, pa);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(d_lists, refs.data(), refs.size() * 4, hipMemcpyHostToDevice, t->st2));
+    }
+    if (!src.empty()) {
+        int32_t *d_src = mig_src(scratch, amount);
+        HIP_TRY(ctx, hipMemcpyAsync(d_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, t->st2));
+        mipx::CutMigArgs ca;
+        ca.n = t->n; ca.count = (int)src.size(); ca.src = d_src; ca.store_pi = t->store_pi; ca.store_pi0 = t->store_pi0;
+        ca.tab_pi = (double *)(msg + L.tab_off); ca.tab_pi0 = ca.tab_pi + (size_t)L.ctab * t->n;
+        hipLaunchKernelGGL(mipx::cutmig_gather, dim3((unsigned)((src.size() + 3) / 4)), dim3(256), 0, t->st2, ca);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(msg + L.meta_off, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, t->st2));
+    HIP_TRY(ctx, hipStreamSynchronize(t->st2));
+    t->cm_nodes_sent += with_cuts;
+    t->cm_rows_sent += (int64_t)src.size();
+    *count = cnt;
+    *table_rows = (int64_t)src.size();
+    return MIPX_OK;
+}
+
+// receiver half, cut mode: as mig_unpack, and the table fills the next rows of this rank's migration region
+int mig_unpack_cuts(mipx_tree *t, const MigLayout &L, char *msg, int32_t *scratch, int64_t amount, int64_t *count) {
+    mipx_ctx *ctx = t->ctx;
+    std::vector<double> meta(L.nmeta, 0.0);
+    std::vector<int32_t> slots;
+    HIP_TRY(ctx, hipMemcpy(meta.data(), msg + L.meta_off, meta.size() * 8, hipMemcpyDeviceToHost));
+    const int64_t cnt = (int64_t)meta[0], rows = (int64_t)meta[L.nmeta - 1];
+    if (cnt < 0 || cnt > amount || rows < 0 || rows > L.ctab) return fail(ctx, MIPX_EHIP, "tree: corrupt migration message");
+    for (int64_t k = 0; k < cnt; k++) {
+        const double nc = meta[1 + 6 * (size_t)k + 5];
+        if (!(nc >= 0 && nc <= L.kc)) return fail(ctx, MIPX_EHIP, "tree: corrupt migration message");
+    }
+    // (the table was capped by the region rows this rank reported in its record, [13])
+    if (rows > t->cm_rows - t->cm_used)
+        return fail(ctx, MIPX_ENOMEM, "tree: cut store region too small for the migrated nodes (raise the rows of "
+                                      "mipx_tree_set_cut_migration)");
+    if ((int64_t)t->free_slots.size() < cnt)
+        return fail(ctx, MIPX_ENOMEM, "tree: node pool too small for the migrated nodes (raise pool_capacity)");
+    if (t->child_recorded) HIP_TRY(ctx, hipStreamWaitEvent(t->st2, t->ev_child, 0));
+    for (int64_t k = 0; k < cnt; k++) {
+        const double *mrec = meta.data() + 1 + 6 * k;
+        NodeRec nd;
+        nd.dual_bound = mrec[0]; nd.b_val = mrec[1]; nd.depth = (int32_t)mrec[2];
+        nd.b_idx = (int32_t)mrec[3]; nd.b_dir = (int32_t)mrec[4];
+        nd.key = t->search == 0 ? nd.dual_bound : -(double)nd.depth;
+        nd.anchor = -1; nd.born = (int32_t)t->steps; nd.ncut = (int32_t)mrec[5];
+        nd.slot = t->free_slots.back();
+        t->free_slots.pop_back();
+        slots.push_back(nd.slot);
+        t->nodes.push_back(nd);
+        tree_push(t, (int64_t)t->nodes.size() - 1);
+    }
+    if (cnt > 0) {
+        const int64_t base = t->store_cap - t->cm_rows + t->cm_used;
+        int32_t *d_bad = mig_bad(L, scratch, amount);
+        int32_t bad = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(scratch, slots.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, t->st2));
+        HIP_TRY(ctx, hipMemsetAsync(d_bad, 0, 4, t->st2));
+        mipx::PackArgs pa = mig_args(t, L, msg, scratch);
+        pa.count = (int)cnt;
+        hipLaunchKernelGGL(mipx::unpack_nodes, dim3((unsigned)cnt), dim3(256), 0, t->st2, pa);
+        HIP_TRY(ctx, hipGetLastError());
+        mipx::CutMigArgs ca;
+        ca.n = t->n; ca.kc = L.kc; ca.slot = scratch; ca.pool_ncut = t->pool_ncut; ca.pool_ids = t->pool_ids;
+        ca.lists = (int32_t *)(msg + L.refs_off); ca.store_pi = t->store_pi; ca.store_pi0 = t->store_pi0;
+        ca.tab_pi = (double *)(msg + L.tab_off); ca.tab_pi0 = ca.tab_pi + (size_t)L.ctab * t->n;
+        ca.base = base; ca.ctab = (int)rows; ca.bad = d_bad;
+        ca.count = (int)cnt;
+        hipLaunchKernelGGL(mipx::cutmig_unpack_lists, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, t->st2, ca);
+        HIP_TRY(ctx, hipGetLastError());
+        if (rows > 0) {
+            ca.count = (int)rows;
+            hipLaunchKernelGGL(mipx::cutmig_scatter, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, t->st2, ca);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, t->st2));
+        HIP_TRY(ctx, hipStreamSynchronize(t->st2));
+        t->cm_used += rows;
+        t->cm_rows_received += rows;
+        if (bad) return fail(ctx, MIPX_EHIP, "tree: corrupt cut lists in a migration message");
+    }
+    *count = cnt;
+    return MIPX_OK;
+}
+
+int x_migrate(mipx_tree *t, int from, int to, int64_t amount, int64_t ctab) {
     mipx_comm *c = t->comm;
     const int me = c->rank;
     if (me != from && me != to) return MIPX_OK;
-    const MigLayout L = mig_layout(t, amount);
+    const MigLayout L = mig_layout(t, amount, ctab);
     char *msg = nullptr;
-    int rc = comm_msg_buffer(c, L.bytes + (size_t)amount * 4, &msg);   // (+ the slot list of the pack kernels)
+    int rc = comm_msg_buffer(c, L.bytes + L.scratch, &msg);   // (+ the slot list of the pack kernels)
     if (rc) return rc;
     int32_t *d_slots = (int32_t *)(msg + L.bytes);
     int64_t cnt = 0;
     if (me == from) {
         std::vector<int32_t> slots;
-        if ((rc = mig_pack(t, L, msg, d_slots, amount, slots, &cnt))) return rc;
+        int64_t rows = 0;
+        if (L.kc > 0) rc = mig_pack_cuts(t, L, msg, d_slots, amount, slots, &cnt, &rows);
+        else rc = mig_pack(t, L, msg, d_slots, amount, slots, &cnt);
+        if (rc) return rc;
         if ((rc = comm_send_dev(c, to, msg, L.bytes))) return rc;
         for (int32_t sl : slots) t->free_slots.push_back(sl);
         t->nodes_sent += cnt;
     } else {
         if ((rc = comm_recv_dev(c, from, msg, L.bytes))) return rc;
-        if ((rc = mig_unpack(t, L, msg, d_slots, amount, &cnt))) return rc;
+        if (L.kc > 0) rc = mig_unpack_cuts(t, L, msg, d_slots, amount, &cnt);
+        else rc = mig_unpack(t, L, msg, d_slots, amount, &cnt);
+        if (rc) return rc;
         t->nodes_received += cnt;
     }
     return MIPX_OK;
@@ -1965,8 +2194,16 @@ void x_decide(int W, int n, const double *records, double mip_gap, bool allow_mi
     out->reason = any_fatal ? 5 : sums[4] == 0 ? 1 : any_stop ? 2 : (gap >= 0 && gap <= mip_gap) ? 3 : all_finished ? 4 : 0;
     out->done = out->reason != 0;
     out->n_moves = 0;
+    // with cut rounds ([15]) nodes move only when every rank takes cut rows the same way ([14]: kc, 0 = off)
+    bool cut_ok = true;
+    for (int r = 0; r < W; r++)
+        if (rec(r)[15] != 0.0) cut_ok = false;
+    if (!cut_ok) {
+        cut_ok = rec(0)[14] > 0.0;
+        for (int r = 0; r < W; r++) cut_ok = cut_ok && rec(r)[15] != 0.0 && rec(r)[14] == rec(0)[14];
+    }
     // migration: a rank that cannot fill a batch gets half the surplus of the fullest rank
-    if (!out->done && allow_migration && W > 1) {
+    if (!out->done && allow_migration && cut_ok && W > 1) {
         std::vector<int64_t> open((size_t)W), low((size_t)W), room((size_t)W);
         for (int r = 0; r < W; r++) {
             open[(size_t)r] = (int64_t)rec(r)[2]; low[(size_t)r] = std::max<int64_t>(1, (int64_t)rec(r)[10]);
@@ -2000,7 +2237,7 @@ int x_apply(mipx_tree *t, const char *gathered, bool last) {
     const double inf = std::numeric_limits<double>::infinity();
     auto rec = [&](int r) { return (const double *)(gathered + (size_t)r * len * 8); };
     mipx_exchange_decision D;
-    x_decide(W, t->n, (const double *)gathered, t->x_mip_gap, !t->cuts, &D);
+    x_decide(W, t->n, (const double *)gathered, t->x_mip_gap, true, &D);
     const double best = D.primal;
     const int who = D.incumbent_rank;
     if (best < t->primal || (best == t->primal && best < inf && !t->have_x && who >= 0)) {
@@ -2082,7 +2319,11 @@ int x_apply(mipx_tree *t, const char *gathered, bool last) {
         return MIPX_OK;
     }
     for (int k = 0; k < D.n_moves; k++) {
-        const int rc = x_migrate(t, D.moves[3 * k], D.moves[3 * k + 1], D.moves[3 * k + 2]);
+        // (cut mode: the table rows follow from the receiver's record, the same on both ends; a receiver
+        // gets at most one donation per exchange, so [13] is what its region can take)
+        const int to = D.moves[3 * k + 1];
+        const int64_t ctab = t->cuts ? mig_table_rows(rec(to)[13], D.moves[3 * k + 2], t->kc) : 0;
+        const int rc = x_migrate(t, D.moves[3 * k], to, D.moves[3 * k + 2], ctab);
         if (rc) return rc;
     }
     return MIPX_OK;
@@ -2841,28 +3082,33 @@ int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps) {
 int64_t mipx_tree_migrate_self(mipx_tree *t, int64_t amount) {
     if (!t || amount < 1) return MIPX_EINVAL;
     if (!t->comm) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_migrate_self: no communicator attached");
-    if (t->cuts) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_migrate_self: not with cut rounds");
+    if (t->cuts && t->cm_rows == 0)
+        return fail(t->ctx, MIPX_EINVAL, "mipx_tree_migrate_self: cut rounds without cut migration (mipx_tree_set_cut_migration)");
     for (const StepBuf &S : t->buf)
         if (S.in_flight) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_migrate_self: a step is in flight");
     mipx_comm *c = t->comm;
     mipx_ctx *ctx = t->ctx;
     if (amount > kMaxMigrate) amount = kMaxMigrate;
-    const MigLayout L = mig_layout(t, amount);
+    const int64_t ctab = t->cuts ? mig_table_rows((double)(t->cm_rows - t->cm_used), amount, t->kc) : 0;
+    const MigLayout L = mig_layout(t, amount, ctab);
     const size_t half = (L.bytes + 255) / 256 * 256;
     char *msg = nullptr;
-    int rc = comm_msg_buffer(c, 2 * half + (size_t)amount * 4, &msg);
+    int rc = comm_msg_buffer(c, 2 * half + L.scratch, &msg);
     if (rc) return rc;
     int32_t *d_slots = (int32_t *)(msg + 2 * half);
     std::vector<int32_t> slots;
-    int64_t sent = 0, got = 0;
+    int64_t sent = 0, got = 0, rows = 0;
     const int keep_batch = t->x_batch;
     t->x_batch = 0;   // (a test may move every open node)
-    rc = mig_pack(t, L, msg, d_slots, amount, slots, &sent);
+    if (L.kc > 0) rc = mig_pack_cuts(t, L, msg, d_slots, amount, slots, &sent, &rows);
+    else rc = mig_pack(t, L, msg, d_slots, amount, slots, &sent);
     t->x_batch = keep_batch;
     if (rc) return rc;
     if ((rc = comm_sendrecv_self(c, msg, msg + half, L.bytes))) return rc;
     for (int32_t sl : slots) t->free_slots.push_back(sl);
-    if ((rc = mig_unpack(t, L, msg + half, d_slots, amount, &got))) return rc;
+    if (L.kc > 0) rc = mig_unpack_cuts(t, L, msg + half, d_slots, amount, &got);
+    else rc = mig_unpack(t, L, msg + half, d_slots, amount, &got);
+    if (rc) return rc;
     if (got != sent) return fail(ctx, MIPX_EHIP, "mipx_tree_migrate_self: the count did not survive the round trip");
     t->nodes_sent += sent;
     t->nodes_received += got;
@@ -3056,7 +3302,8 @@ int64_t mipx_tree_cut_store(mipx_tree *t, int64_t capacity, double *pi, double *
     if (hipStreamSynchronize(t->ctx->stream) != hipSuccess) return MIPX_EHIP;
     int32_t cnt = 0;
     if (hipMemcpy(&cnt, t->store_count, 4, hipMemcpyDeviceToHost) != hipSuccess) return MIPX_EHIP;
-    int64_t have = cnt < t->store_cap ? cnt : t->store_cap;
+    const int64_t own = t->store_cap - t->cm_rows;   // (the rank's own appends: not the migration region)
+    int64_t have = cnt < own ? cnt : own;
     const int64_t k = have < capacity ? have : capacity;
     if (pi && k > 0 && hipMemcpy(pi, t->store_pi, (size_t)k * t->n * 8, hipMemcpyDeviceToHost) != hipSuccess) return MIPX_EHIP;
     if (pi0 && k > 0 && hipMemcpy(pi0, t->store_pi0, (size_t)k * 8, hipMemcpyDeviceToHost) != hipSuccess) return MIPX_EHIP;
@@ -3103,6 +3350,63 @@ int mipx_tree_set_host_spill(mipx_tree *t, int64_t max_host_bytes) {
         }
     }
     h.cap = max_host_bytes;
+    return MIPX_OK;
+}
+
+int mipx_tree_set_cut_migration(mipx_tree *t, int64_t rows) {
+    if (!t) return MIPX_EINVAL;
+    mipx_ctx *ctx = t->ctx;
+    if (!t->cuts) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_cut_migration: the tree runs no cut rounds");
+    if (rows < 0) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_cut_migration: negative rows");
+    for (const StepBuf &S : t->buf)
+        if (S.in_flight) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_cut_migration: a step is in flight");
+    if (rows == t->cm_rows) return MIPX_OK;
+    if (t->cm_used > 0)
+        return fail(ctx, MIPX_EINVAL, "mipx_tree_set_cut_migration: the region holds migrated cut rows already");
+    if (rows >= t->store_cap)
+        return fail(ctx, MIPX_EINVAL, "mipx_tree_set_cut_migration: the region must leave rows of the cut store (store_capacity)");
+    if (rows > 0) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        int32_t cnt = 0;
+        HIP_TRY(ctx, hipMemcpy(&cnt, t->store_count, 4, hipMemcpyDeviceToHost));
+        if ((int64_t)cnt > t->store_cap - rows)
+            return fail(ctx, MIPX_EINVAL, "mipx_tree_set_cut_migration: the cut store holds more than store_capacity - rows cuts");
+    }
+    t->cm_rows = rows;
+    return MIPX_OK;
+}
+
+int mipx_tree_cut_rows(mipx_tree *t, int64_t count, const int32_t *ids, double *pi, double *pi0) {
+    if (!t || count < 0 || (count > 0 && !ids)) return MIPX_EINVAL;
+    mipx_ctx *ctx = t->ctx;
+    if (!t->cuts) return fail(ctx, MIPX_EINVAL, "mipx_tree_cut_rows: the tree runs no cut rounds");
+    for (int64_t k = 0; k < count; k++)
+        if (ids[k] < 0 || ids[k] >= t->store_cap) return fail(ctx, MIPX_EINVAL, "mipx_tree_cut_rows: id outside the cut store");
+    if (count == 0) return MIPX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t n = (size_t)t->n;
+    char *blk = nullptr;   // [ids | pi | pi0]
+    const size_t ids_b = pad8((size_t)count * 4);
+    HIP_TRY(ctx, hipMalloc((void **)&blk, ids_b + (size_t)count * (n + 1) * 8));
+    mipx::CutMigArgs ca;
+    ca.n = t->n; ca.count = (int)count; ca.src = (const int32_t *)blk; ca.store_pi = t->store_pi; ca.store_pi0 = t->store_pi0;
+    ca.tab_pi = (double *)(blk + ids_b); ca.tab_pi0 = ca.tab_pi + (size_t)count * n;
+    int rc = MIPX_OK;
+    if (hipMemcpy(blk, ids, (size_t)count * 4, hipMemcpyHostToDevice) != hipSuccess) rc = MIPX_EHIP;
+    if (!rc) {
+        hipLaunchKernelGGL(mipx::cutmig_gather, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, ca);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = MIPX_EHIP;
+    }
+    if (!rc && pi && hipMemcpy(pi, ca.tab_pi, (size_t)count * n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = MIPX_EHIP;
+    if (!rc && pi0 && hipMemcpy(pi0, ca.tab_pi0, (size_t)count * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = MIPX_EHIP;
+    (void)hipFree(blk);
+    return rc ? fail(ctx, rc, "mipx_tree_cut_rows: HIP error") : MIPX_OK;
+}
+
+int mipx_tree_cut_migration_stats(mipx_tree *t, int64_t out[4]) {
+    if (!t || !out) return MIPX_EINVAL;
+    out[0] = t->cm_nodes_sent; out[1] = t->cm_rows_sent; out[2] = t->cm_rows_received; out[3] = t->cm_used;
     return MIPX_OK;
 }
 
