@@ -217,6 +217,18 @@ CUTMIG_STATS_KEYS = ('nodes_sent_with_cuts', 'cut_rows_sent', 'cut_rows_received
 # rows of the migration region that cut_migration=True / set_cut_migration(True) reserve
 DEFAULT_CUT_MIGRATION_ROWS = 1 << 16
 
+# ... and those of include/mipx_dualfn.h (the dual function of a search), which mipx.h includes
+# (tests/test_dual_function_abi.py checks them against that header)
+_DUALFN_SIGNATURES = {
+    'mipx_tree_set_dual_record': (_i, [_vp, _i64, _i, _vp, _vp]),
+    'mipx_tree_dual_function': (_i, [_vp, _i, _vp, _d, _vp]),
+    'mipx_tree_dual_function_stats': (_i, [_vp, _vp]),
+    'mipx_tree_dual_records': (_i64, [_vp, _i64] + [_vp] * 5),
+}
+DUALFN_SYMBOLS = list(_DUALFN_SIGNATURES)
+DUALFN_STATS_KEYS = ('records', 'bytes', 'dropped', 'infeasible_leaves', 'penalized_resolves', 'leaves_without_term',
+                     'record_ms', 'eval_ms')
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -230,7 +242,7 @@ def lib():
             'simple_mip_solver_amd has no CPU fallback.')
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_SPILL_SIGNATURES.items()) +
-                                      list(_CUTMIG_SIGNATURES.items())):
+                                      list(_CUTMIG_SIGNATURES.items()) + list(_DUALFN_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -884,6 +896,49 @@ class Tree:
         d['spill_ms'] /= 1000.0
         d['reload_ms'] /= 1000.0
         return d
+
+    def set_dual_record(self, max_bytes, rows, pos, sign):
+        """Record one dual term per solved node from the first step on, up to max_bytes of device memory
+        (mipx_tree_set_dual_record, include/mipx_dualfn.h; -1: half of the device memory free now).  rows, pos,
+        sign: the LP rows and, per engine row, its LP row and sign (the slack block of the penalised re-solve)."""
+        pos = np.ascontiguousarray(pos, np.int32).reshape(-1)
+        sign = np.ascontiguousarray(sign, np.float64).reshape(-1)
+        assert len(pos) == len(sign) == self.problem.m, 'one (pos, sign) per engine row'
+        self.problem.ctx.check(lib().mipx_tree_set_dual_record(self._h, int(max_bytes), int(rows), _ptr(pos), _ptr(sign)),
+                               'mipx_tree_set_dual_record')
+
+    def dual_function(self, W, M):
+        """f(w) for every row w of W (K x m, engine rows): the dual function's lower bounds
+        (mipx_tree_dual_function)."""
+        W = np.ascontiguousarray(W, np.float64)
+        if W.ndim == 1:
+            W = W[None]
+        assert W.shape[1] == self.problem.m, 'right-hand sides have one entry per engine row'
+        out = np.zeros(W.shape[0])
+        self.problem.ctx.check(lib().mipx_tree_dual_function(self._h, W.shape[0], _ptr(W), float(M), _ptr(out)),
+                               'mipx_tree_dual_function')
+        return out
+
+    def dual_function_stats(self):
+        """dict(records, bytes, dropped, infeasible_leaves, penalized_resolves, leaves_without_term, record_ms,
+        eval_ms) (mipx_tree_dual_function_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_dual_function_stats(self._h, _ptr(out)), 'mipx_tree_dual_function_stats')
+        d = dict(zip(DUALFN_STATS_KEYS, (int(v) for v in out)))
+        d['record_ms'] /= 1000.0
+        d['eval_ms'] /= 1000.0
+        return d
+
+    def dual_records(self):
+        """dict(node, parent, status, t, y) of every record in store order (mipx_tree_dual_records)."""
+        R = self.dual_function_stats()['records']
+        node, parent = np.zeros(R, np.int64), np.zeros(R, np.int64)
+        status, tval = np.zeros(R, np.int32), np.zeros(R)
+        y = np.zeros((R, self.problem.m))
+        got = lib().mipx_tree_dual_records(self._h, R, _ptr(node), _ptr(parent), _ptr(status), _ptr(tval), _ptr(y))
+        if got < 0:
+            self.problem.ctx.check(int(got), 'mipx_tree_dual_records')
+        return dict(node=node, parent=parent, status=status, t=tval, y=y)
 
     def set_cut_migration(self, rows):
         """Reserve the top `rows` rows of the cut store for the cut rows of nodes received from other ranks, so

@@ -20,6 +20,7 @@
 #include "tree_kernels.hip.h"
 #include "finish_kernels.hip.h"
 #include "cutmig_kernels.hip.h"
+#include "dualfn_kernels.hip.h"
 
 struct NodeRec {
     double key;          // queue key: dual bound (best first) or -depth (depth first)
@@ -269,6 +270,11 @@ struct StepBuf {
     // into their new rows on the launch stream before the node LPs read them
     char *h_rl = nullptr, *d_rl = nullptr;
     int rl_n = 0;
+    // dual function (recording on): the node LPs' row duals, the record kernel's entries and its timing
+    double *df_y = nullptr;
+    char *df_h = nullptr, *df_d = nullptr;
+    hipEvent_t df_e0 = nullptr, df_e1 = nullptr;
+    bool df_timed = false;
     int B = 0;
     bool in_flight = false;
     double inflight_min = std::numeric_limits<double>::infinity();   // lowest inherited bound of the batch (exchange record)
@@ -293,6 +299,40 @@ struct HostSpill {
     std::vector<int32_t> loc_free;
     int64_t bytes = 0, peak = 0, spilled = 0, reloaded = 0, on_host = 0, events = 0;
     double spill_us = 0.0, reload_us = 0.0;
+};
+
+// Dual function (include/mipx_dualfn.h): one record (y, t) per node solved to optimality, appended to a
+// store in device memory; the infeasible nodes' bounds and basis codes beside it.  The per-node arrays
+// exist only while recording is on (NodeRec keeps its size).
+struct DualFn {
+    bool on = false;
+    int64_t cap = 0, bytes = 0;          // byte cap, bytes in use (records and infeasible rows)
+    int rows = 0;                        // the LP's own rows (slacks of the penalised LP)
+    std::vector<int32_t> pos;            // per engine row: its LP row, and the sign
+    std::vector<double> sign;
+    std::vector<int64_t> parent;         // per node id: parent id (-1 root)
+    std::vector<int32_t> rec;            // per node id: its record (-1 none)
+    std::vector<uint8_t> haschild;       // per node id
+    std::vector<int64_t> rec_node;       // per record: node id
+    std::vector<int32_t> rec_status;     // per record: 0 node LP, 1 penalised re-solve
+    double *d_y = nullptr, *d_t = nullptr;   // the store: rows of m, and t
+    int64_t rcap = 0;                    // rows allocated
+    std::vector<int64_t> inf_node;       // infeasible nodes with saved rows, in order
+    int64_t inf_done = 0;                // ... the first inf_done of them have been re-solved (or given up)
+    double *d_il = nullptr, *d_iu = nullptr;  // their rows: n bounds each, nv codes
+    int8_t *d_iv = nullptr;
+    int64_t icap = 0;
+    int64_t dropped = 0, resolves = 0, noterm = 0;
+    double record_us = 0.0, eval_us = 0.0;
+    // per step buffer: the node LPs' row duals (levels x max_batch x m), the entry lists (staged pinned)
+    size_t ystep_rows = 0;
+    // evaluation: the lineage arrays on the device, rebuilt when the records or the tree changed
+    bool dirty = true;
+    int32_t *d_prec = nullptr, *d_order = nullptr, *d_lvl = nullptr, *d_leaf = nullptr;
+    int nlvl = 0, nleaf = 0, bare = 0;
+    double *d_V = nullptr, *d_W = nullptr, *d_out = nullptr;
+    size_t vcap = 0, wcap = 0, ocap = 0;
+    std::vector<double> hostA;           // A (m x n), read back once for the penalised LP
 };
 
 struct mipx_tree {
@@ -420,6 +460,7 @@ struct mipx_tree {
     double phase_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // MIPX_TREE_PROFILE=1: host-side breakdown
     std::vector<double> root_l, root_u;   // the root's bounds (compact records store the differences)
     HostSpill hs;
+    DualFn df;
     // cut migration (mipx_tree_set_cut_migration): the top cm_rows rows of the cut store take the cut rows
     // of nodes received from other ranks, filled in order by the migration code (host-side fill level)
     int64_t cm_rows = 0, cm_used = 0;
@@ -513,7 +554,8 @@ struct CutLaunch {
 int launch_lp(mipx_tree *t, int batch, const double *l, const double *u, const int8_t *v,
               const int32_t *slot, int max_iter, int32_t *status, double *obj, double *x,
               int8_t *vout, int32_t *iters, int32_t *npiv, hipStream_t stream = nullptr,
-              const StepBuf *dive = nullptr, const int32_t *asel = nullptr, const CutLaunch *cl = nullptr) {
+              const StepBuf *dive = nullptr, const int32_t *asel = nullptr, const CutLaunch *cl = nullptr,
+              double *y_out = nullptr) {
     mipx::LpArgs a = problem_args(t->prob, !(cl != nullptr && cl->no_anchor));
     if (dive) {  // in-place dive: K4's rule inside K1, level p's children at positions p * batch ..
         a.dive = dive->dive; a.dive_off = batch; a.rule = t->rule; a.n_int = t->n_int;
@@ -541,8 +583,11 @@ int launch_lp(mipx_tree *t, int batch, const double *l, const double *u, const i
         if (cl->dT) { a.dbg_T = cl->dT; a.dbg_vec = cl->dvec; a.dbg_idx = cl->didx; a.dbg_all = 1; }
         m_rows = cl->m_rows;
     }
+    if (y_out) a.y = y_out;   // row duals of every output position (dual function recording)
     return launch_lp_any(t->prob, a, batch, stream, m_rows);
 }
+
+#include "dualfn.hip.h"
 
 // Device -> host copies of the step loop go through the side stream, never the null stream: a
 // null-stream copy shares a hardware queue with whatever the runtime mapped there, and in a
@@ -1060,7 +1105,8 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
     // the root alone, never solved: one cold LP (above the register tiles it is spread over the chip, K1c)
     t->cold_launch = B == 1 && t->nodes.size() == 1 && S.recs[0].depth == 0 && S.recs[0].b_idx == -1 && !t->prob->anchor_on;
     rc = launch_lp(t, B, t->pool_l, t->pool_u, t->pool_v, S.d_slot, 0, S.d_status, S.d_obj,
-                   S.d_x, S.d_vout, S.d_iters, S.d_npiv, nullptr, S.dive ? &S : nullptr, S.d_slot + B);
+                   S.d_x, S.d_vout, S.d_iters, S.d_npiv, nullptr, S.dive ? &S : nullptr, S.d_slot + B, nullptr,
+                   t->df.on ? S.df_y : nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(S.e1, st));
     if (S.fast) {
@@ -1600,8 +1646,12 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
     // (best first on the bucket queue: the pushes of the step are collected and queued together below)
     const bool defer_push = t->use_bq && t->search == 0;
     t->pend.clear();
+    const bool rec = t->df.on;
+    std::vector<DfEntry> df_recs, df_infs;   // (dual function: this step's solved and infeasible nodes)
     auto evaluate = [&](int64_t id, int pos, int32_t slot, int level, int depth, int32_t anchor, int &err) -> int64_t {
         t->evaluated++;
+        if (rec && status[pos] == 0) df_recs.push_back({pos, slot, id});
+        if (rec && status[pos] == 1) df_infs.push_back({pos, slot, id});
         const bool lp_feasible = status[pos] == 0 || status[pos] == 2;
         if (status[pos] == 2) t->unbounded = true;
         int branched_on = -1;
@@ -1640,6 +1690,10 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
                     g_hp_rec += __rdtsc() - r0_;
 #endif
                     const int64_t cid = (int64_t)t->nodes.size() - 1;
+                    if (rec) {
+                        t->df.parent.push_back(id); t->df.rec.push_back(-1); t->df.haschild.push_back(0);
+                        t->df.haschild[(size_t)id] = 1;
+                    }
                     if (take_dive && dir == ddir[pos]) {
                         dive_child = cid;  // already solved: never enters the queue
                     } else if (defer_push) {
@@ -1752,6 +1806,15 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
             t->child_recorded = true;
         } else {
             HIP_TRY(ctx, hipStreamSynchronize(st));
+        }
+    }
+    if (rec) {   // the step's records, behind its children records (the dive children's rows hold their bounds)
+        hipStream_t cs = overlapped ? t->st3 : st;
+        if ((rc = df_step(t, S, cs, df_recs, df_infs))) return rc;
+        if (overlapped && !(df_recs.empty() && df_infs.empty())) {
+            HIP_TRY(ctx, hipEventRecord(t->ev_child, t->st3));   // (the next launch, and so the rows' reuse, waits)
+            t->child_pending = true;
+            t->child_recorded = true;
         }
     }
     for (int32_t sl : dive_slots) t->free_slots.push_back(sl);
@@ -2623,6 +2686,19 @@ void mipx_tree_destroy(mipx_tree *t) {
             if (S.d_rl) (void)hipFree(S.d_rl);
         }
     }
+    {
+        DualFn &df = t->df;
+        void *dp[] = {df.d_y, df.d_t, df.d_il, df.d_iu, df.d_iv, df.d_prec, df.d_order, df.d_lvl, df.d_leaf, df.d_V, df.d_W, df.d_out};
+        for (void *q : dp)
+            if (q) (void)hipFree(q);
+        for (StepBuf &S : t->buf) {
+            if (S.df_y) (void)hipFree(S.df_y);
+            if (S.df_d) (void)hipFree(S.df_d);
+            if (S.df_h) (void)hipHostFree(S.df_h);
+            if (S.df_e0) (void)hipEventDestroy(S.df_e0);
+            if (S.df_e1) (void)hipEventDestroy(S.df_e1);
+        }
+    }
     if (t->h_pairs) (void)hipHostFree(t->h_pairs);
     if (t->h_pres) (void)hipHostFree(t->h_pres);
     if (t->h_tab) (void)hipHostFree(t->h_tab);
@@ -2700,6 +2776,10 @@ int mipx_tree_solve(mipx_tree *t, int64_t node_limit, double mip_gap, double max
     if (t->hs.cap > 0 && t->capacity < 2 * spill_headroom(t) + 1)
         return fail(ctx, MIPX_EINVAL, "mipx_tree_solve: pool_capacity below the host spill headroom (see mipx_spill.h)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (t->df.on) {
+        const int drc = df_prepare(t);
+        if (drc) return drc;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     const double inf = std::numeric_limits<double>::infinity();
     double ph0[8], pr0[4];
@@ -3045,6 +3125,7 @@ int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps) {
     if (c && c->ctx != t->ctx) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: communicator of another context");
     if (c && (t->hs.cap > 0 || t->hs.on_host > 0))
         return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the host spill (mipx_tree_set_host_spill)");
+    if (c && t->df.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the dual function (mipx_tree_set_dual_record)");
     t->comm = c;
     t->x_every = c ? every_steps : 0;
     if (!c) return MIPX_OK;
@@ -3419,3 +3500,5 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 }
 
 }  // extern "C"
+
+#include "dualfn_api.hip.h"
