@@ -380,7 +380,7 @@ struct Smem {
     double va[NP];      // nonbasic values a + b*M by column
     double vb[NP];
     double d[NP];       // staging of the borders at setup / output (they live in the control wave's
-    double key[NP];     //   registers in between); key: x assembly
+    alignas(16) double key[NP];  //   registers in between); key: x assembly
     double cvec[NP];    // objective coefficients (the objective is re-summed from x at the end)
     double beta0[MP];
     double ba[4 * NW * R];
@@ -398,6 +398,11 @@ struct Smem {
     int nfake0;
     double objv;        // objective of the LP just solved (worked out by tableau wave 0 for the control wave)
     int dive_code;      // branching variable of the in-place dive, -1: none
+    int xseq;           // passes whose x is complete in s.key (control wave -> tableau wave 0)
+    // a level's report on its way from the control wave to the tableau waves (engine output path)
+    alignas(16) int8_t vst[NP + MP];  // basis codes by variable index
+    int ostatus, oiters, onpiv, odvar, oddir;
+    double odval;
     int seq;            // pivot column parts published so far (one count per tableau wave and column)
     int pos[NP + MP];   // column of each variable in the starting tableau, -1 if basic
     int8_t wantb[NP + MP];
@@ -888,7 +893,7 @@ __device__ __forceinline__ void lp_dual_simplex_role(const LpArgs &g, Smem<NW, R
             }
         }
     }
-    if (tid == 0) s.seq = 0;
+    if (tid == 0) { s.seq = 0; s.xseq = 0; }
     if (DIVE && g.dive_preset && tid < g.dive) {   // level tid + 1 has no LP, level tid no decision (yet)
         g.status[(size_t)node + (size_t)(tid + 1) * (size_t)g.dive_off] = -1;
         g.dive_var[(size_t)tid * (size_t)g.dive_off + node] = -1;
@@ -1215,6 +1220,7 @@ __device__ __forceinline__ void lp_dual_simplex_role(const LpArgs &g, Smem<NW, R
             constexpr bool kShadow = NW >= 7;
             MIPX_LEAVE_SELECT();
             if constexpr (!kShadow) MIPX_LEAVE_FETCH();
+            KPROF_OUT_MARK(13);
             __syncthreads();  // A
             for (;;) {
                 if (sel_win >> 16) { const int cmd = sel_win >> 16; status = cmd == 1 ? 0 : cmd == 3 ? 2 : 3; break; }
@@ -1428,15 +1434,18 @@ __device__ __forceinline__ void lp_dual_simplex_role(const LpArgs &g, Smem<NW, R
     __syncthreads();
     tprev = clock64();   // (the dump above is the profiler's own cost)
 #endif
-    // The engine's steps want neither row duals nor a tableau dump: then everything below is the control
-    // wave's alone -- it holds both borders in registers -- and the tableau waves go straight to the barrier
-    // behind which the dive's decision is known.  (The general path hands the borders over through LDS and
-    // shares the loops out: three more barriers, each with a serial stretch before it.)  Same arithmetic,
+    // The engine's steps want neither row duals nor a tableau dump.  Then only the dive's decision is on the
+    // control wave's path: it scatters x by variable index into s.key, hands it to tableau wave 0 (which folds
+    // the objective meanwhile) and runs K4's rule; both meet at the one barrier behind which the decision is
+    // known.  What the level reports -- x, the basis, the scalars -- waits in LDS and goes to HBM from the
+    // tableau waves behind that barrier, while the control wave starts the next level (its next write to s.key
+    // or the staging comes after the next barrier A).  (The general path hands the borders over through LDS
+    // and shares the loops out: three more barriers, each with a serial stretch before it.)  Same arithmetic,
     // same order: x by variable index, the objective's fold-in-half sum, K4's rule.
     if (g.y == nullptr && g.dbg_T == nullptr) {
     const bool more = DIVE && pass < g.dive && solve;  // (DIVE = false: the pass loop folds away)
+    constexpr int PER = NP / 64;
     if (ctl) {
-        constexpr int PER = NP / 64;
         static_assert(PER == PJ, "one column per lane and slot");
 #pragma unroll
         for (int kk = 0; kk < PJ; kk++) {
@@ -1451,23 +1460,85 @@ __device__ __forceinline__ void lp_dual_simplex_role(const LpArgs &g, Smem<NW, R
             const int v = rM[kk] >> 2;
             if (i < m && v < n) s.key[v] = fma(rBb[kk], kMReport, rBa[kk]);
         }
-        if (g.vstat_out) {   // the basis, straight from the registers
-            int8_t *vo = g.vstat_out + onode * (size_t)(n + ms);
+        // x is complete for tableau wave 0 (one wave: LDS executes its writes in order, the count comes last)
+        if (lane == 0) __hip_atomic_store(&s.xseq, pass + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        // the candidates' values for the rule, asked for first; the level's report is staged while they arrive:
+        // the basis codes by variable index and the scalars
+        double cx[PJ];
+#pragma unroll
+        for (int kk = 0; kk < PJ; kk++) cx[kk] = s.key[ci[kk]];
+        if (g.vstat_out) {
 #pragma unroll
             for (int kk = 0; kk < PI; kk++)
-                if (lane + 64 * kk < m) vo[rM[kk] >> 2] = 1;
+                if (lane + 64 * kk < m) s.vst[rM[kk] >> 2] = 1;
 #pragma unroll
             for (int kk = 0; kk < PJ; kk++)
-                if (lane + 64 * kk < n) vo[cM[kk] >> 3] = (cM[kk] & 3) ? 2 : 3;
+                if (lane + 64 * kk < n) s.vst[cM[kk] >> 3] = (cM[kk] & 3) ? 2 : 3;
         }
-        // (one wave: its LDS writes above are in order before the reads below)
+        if (lane == 0) {
+            s.ostatus = status;
+            s.oiters = iters;
+            s.onpiv = npiv;
+        }
+        KPROF_OUT_MARK(9);
+        int code = -1;  // the rule's choice; the cutoff test needs the objective and comes behind the barrier
+        double dval = 0.0;
+        if (more && status == 0) {
+            double bk = -1.0;
+            int bp = kNoCand;
+            bool probe = false;  // some fractional candidate has no pseudo-cost entry (one ballot for all slots)
+#pragma unroll
+            for (int kk = 0; kk < PJ; kk++) {
+                const int k = lane + 64 * kk;
+                const double v = cx[kk];
+                const double fl = floor(v), ce = ceil(v);
+                const double dist = fmin(v - fl, ce - v);
+                const bool frac = cv[kk] && dist > kVarEps;
+                const double key = g.rule == 0 ? dist : fmin(ccr[kk] * (ce - v), ccl[kk] * (v - fl));
+                keep_max(bk, bp, key, k, frac && che[kk]);
+                probe |= frac && !che[kk];
+            }
+            double km;
+            const int win = wave_argmax_pos(bk, bp, km);
+            if (win != kNoCand && __ballot(probe) == 0ull) {
+                const int wl = win & 63, wk = win >> 6;
+                int t_i;
+                double t_l, t_r, t_v;
+                MIPX_PICK(t_i, ci, PJ, wk);
+                MIPX_PICK(t_l, ccl, PJ, wk);
+                MIPX_PICK(t_r, ccr, PJ, wk);
+                MIPX_PICK(t_v, cx, PJ, wk);
+                dvar = __builtin_amdgcn_readlane(t_i, wl);
+                const double wcl = readlane_f64(t_l, wl), wcr = readlane_f64(t_r, wl);
+                const double v = readlane_f64(t_v, wl);  // = s.key[dvar]
+                const double fl = floor(v), ce = ceil(v);
+                if (g.rule == 0) ddir = (v - fl <= ce - v) ? 0 : 1;
+                else ddir = (wcl * (v - fl) <= wcr * (ce - v)) ? 0 : 1;
+                dbound = ddir == 0 ? fl : ce;
+                dval = v;
+                bool mine = false;  // a bound change in place needs the variable basic
+#pragma unroll
+                for (int kk = 0; kk < PI; kk++) mine |= (lane + 64 * kk < m) && (rM[kk] >> 2) == dvar;
+                if (__ballot(mine) != 0ull) code = dvar;
+            }
+        }
+        KPROF_OUT_MARK(12);
+        if (lane == 0) {
+            s.dive_code = code;
+            s.odvar = dvar;
+            s.oddir = ddir;
+            s.odval = dval;
+        }
+    } else if (tw == 0) {
+        // obj = fold-in-half sum of c_j x_j over the padded power-of-two length, once x is in s.key
+        while (__hip_atomic_load(&s.xseq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= pass)
+            __builtin_amdgcn_s_sleep(1);
+        KPROF_OUT_MARK(9);
         double p[PER];
 #pragma unroll
         for (int k = 0; k < PER; k++) {
             const int j = lane + 64 * k;
-            const double xj = s.key[j];
-            if (g.x && j < n) g.x[onode * n + j] = xj;
-            p[k] = j < n ? s.cvec[j] * xj : 0.0;
+            p[k] = j < n ? s.cvec[j] * s.key[j] : 0.0;
         }
 #pragma unroll
         for (int h = PER / 2; h >= 1; h >>= 1) {
@@ -1481,63 +1552,77 @@ __device__ __forceinline__ void lp_dual_simplex_role(const LpArgs &g, Smem<NW, R
         sum = sum + xor4_f64(sum);
         sum = sum + xor2_f64(sum);
         sum = sum + xor1_f64(sum);
-        const double objv = uniform_f64(sum);
-        int code = -1;
-        double dval = 0.0;
-        if (more && status == 0 && objv < g.dive_cutoff) {
-            double bk = -1.0;
-            int bp = kNoCand, nprobe = 0;
-#pragma unroll
-            for (int kk = 0; kk < PJ; kk++) {
-                const int k = lane + 64 * kk;
-                const double v = s.key[ci[kk]];
-                const double fl = floor(v), ce = ceil(v);
-                const double dist = fmin(v - fl, ce - v);
-                const bool frac = cv[kk] && dist > kVarEps;
-                const double key = g.rule == 0 ? dist : fmin(ccr[kk] * (ce - v), ccl[kk] * (v - fl));
-                keep_max(bk, bp, key, k, frac && che[kk]);
-                nprobe += __popcll(__ballot(frac && !che[kk]));
-            }
-            double km;
-            const int win = wave_argmax_pos(bk, bp, km);
-            if (win != kNoCand && nprobe == 0) {
-                const int wl = win & 63, wk = win >> 6;
-                int t_i;
-                double t_l, t_r;
-                MIPX_PICK(t_i, ci, PJ, wk);
-                MIPX_PICK(t_l, ccl, PJ, wk);
-                MIPX_PICK(t_r, ccr, PJ, wk);
-                dvar = __builtin_amdgcn_readlane(t_i, wl);
-                const double wcl = readlane_f64(t_l, wl), wcr = readlane_f64(t_r, wl);
-                const double v = uniform_f64(s.key[dvar]);
-                const double fl = floor(v), ce = ceil(v);
-                if (g.rule == 0) ddir = (v - fl <= ce - v) ? 0 : 1;
-                else ddir = (wcl * (v - fl) <= wcr * (ce - v)) ? 0 : 1;
-                dbound = ddir == 0 ? fl : ce;
-                dval = v;
-                bool mine = false;  // a bound change in place needs the variable basic
-#pragma unroll
-                for (int kk = 0; kk < PI; kk++) mine |= (lane + 64 * kk < m) && (rM[kk] >> 2) == dvar;
-                if (__ballot(mine) != 0ull) code = dvar;
-            }
-        }
-        if (lane == 0) {
-            if (g.obj) g.obj[onode] = status == 1 ? INF : objv;
-            if (g.status) g.status[onode] = status;
-            if (g.iters) g.iters[onode] = iters;
-            if (g.npivots) g.npivots[onode] = npiv;
-            if (code >= 0) {
-                const size_t di = (size_t)pass * (size_t)g.dive_off + node;
-                g.dive_var[di] = dvar;
-                g.dive_dir[di] = ddir;
-                g.dive_val[di] = dval;
-            }
-            s.dive_code = code;
-        }
+        if (lane == 0) s.objv = sum;
+        KPROF_OUT_MARK(10);
     }
-    if (!more) break;
     KPROF_OUT_MARK(14);
     __syncthreads();
+    // every wave: the decision (the rule's choice, if the node is below the cutoff)
+    const double objv = uniform_f64(s.objv);
+    int code = __builtin_amdgcn_readfirstlane(s.dive_code);
+    if (!(objv < g.dive_cutoff)) code = -1;
+    if (!ctl) {
+        // the report to HBM: x in 16-byte pieces, the basis a dword per lane, the scalars from the last lane.
+        // The output pointers are read here, through an opaque copy of the kernel-argument pointer (g is the
+        // kernel's only argument, at offset 0): hoisted above the solve they would hold SGPRs across it (spilled).
+        auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kp));
+        const LpArgs __attribute__((address_space(4))) *go = (const LpArgs __attribute__((address_space(4))) *)kp;
+        const int ttid = tid - 64;
+        constexpr int NTT = 64 * NW;
+        double *gx = go->x;
+        if (gx) {
+            double *xo = gx + onode * n;
+            if ((n & 1) == 0 && (reinterpret_cast<uintptr_t>(gx) & 15) == 0) {
+#pragma unroll
+                for (int t = 0; t < (NP / 2 + NTT - 1) / NTT; t++) {
+                    const int j = 2 * (ttid + t * NTT);
+                    if (j < n) *reinterpret_cast<double2 *>(xo + j) = *reinterpret_cast<const double2 *>(&s.key[j]);
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < (NP + NTT - 1) / NTT; t++) {
+                    const int j = ttid + t * NTT;
+                    if (j < n) xo[j] = s.key[j];
+                }
+            }
+        }
+        const int rt = NTT - 1 - ttid;  // (the basis from the last waves: x keeps the first ones busy)
+        int8_t *gv = go->vstat_out;
+        if (gv) {
+            int8_t *vo = gv + onode * (size_t)(n + ms);
+            const int nb = n + m;
+            int k0 = 0;
+            if (((n + ms) & 3) == 0 && (reinterpret_cast<uintptr_t>(gv) & 3) == 0) {
+                k0 = nb & ~3;
+#pragma unroll
+                for (int t = 0; t < ((NP + MP) / 4 + NTT - 1) / NTT; t++) {
+                    const int k = 4 * (rt + t * NTT);
+                    if (k < k0) *reinterpret_cast<int32_t *>(vo + k) = *reinterpret_cast<const int32_t *>(&s.vst[k]);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < (NP + MP + NTT - 1) / NTT; t++) {
+                const int k = k0 + rt + t * NTT;
+                if (k < nb) vo[k] = s.vst[k];
+            }
+        }
+        if (rt == 0) {
+            const int st = s.ostatus;
+            if (go->obj) go->obj[onode] = st == 1 ? INF : objv;
+            if (go->status) go->status[onode] = st;
+            if (go->iters) go->iters[onode] = s.oiters;
+            if (go->npivots) go->npivots[onode] = s.onpiv;
+            if (code >= 0) {
+                const size_t di = (size_t)pass * (size_t)go->dive_off + node;
+                go->dive_var[di] = s.odvar;
+                go->dive_dir[di] = s.oddir;
+                go->dive_val[di] = s.odval;
+            }
+        }
+        KPROF_OUT_MARK(12);
+    }
+    if (!more || code < 0) break;
     } else {
     if (ctl) {
         // the borders go to LDS for the output loops; x by variable index (s.key) straight from the registers
@@ -1698,9 +1783,9 @@ __device__ __forceinline__ void lp_dual_simplex_role(const LpArgs &g, Smem<NW, R
     if (!more) break;
     KPROF_OUT_MARK(14);
     __syncthreads();
-    }
-    }
     if (__builtin_amdgcn_readfirstlane(s.dive_code) < 0) break;
+    }
+    }
     KPROF_MARK(11);  // outputs of the node + the branching rule
     pass++;
     onode += (size_t)g.dive_off;
