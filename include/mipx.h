@@ -531,5 +531,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_spill.h"   /* host spill of the frontier engine and its compact node records */
 #include "mipx_cutmig.h"  /* migration of nodes with their cut rows in cut-round mode */
 #include "mipx_dualfn.h"  /* the dual function of a frontier-engine search */
+#include "mipx_treerec.h" /* the search tree of a frontier-engine search, kept as records */
 
 #endif /* MIPX_H */

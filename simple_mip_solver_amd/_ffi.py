@@ -230,6 +230,21 @@ DUALFN_STATS_KEYS = ('records', 'bytes', 'dropped', 'infeasible_leaves', 'penali
                      'record_ms', 'eval_ms')
 
 
+# ... and those of include/mipx_treerec.h (the search tree kept as records), which mipx.h includes
+# (tests/test_tree_record_abi.py checks them against that header)
+_TREEREC_SIGNATURES = {
+    'mipx_tree_set_tree_record': (_i, [_vp, _i]),
+    'mipx_tree_records': (_i64, [_vp, _i64, _i64] + [_vp] * 9),
+    'mipx_tree_node_bounds': (_i, [_vp, _i64, _vp, _vp, _vp]),
+    'mipx_tree_node_solve': (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'mipx_tree_record_stats': (_i, [_vp, _vp]),
+}
+TREEREC_SYMBOLS = list(_TREEREC_SIGNATURES)
+TREEREC_STATS_KEYS = ('nodes', 'host_bytes', 'device_bytes', 'materialised', 'resolved', 'query_ms')
+# flags of a record (MIPX_TR_* of the header)
+TR_MIP_FEASIBLE, TR_HAS_CHILDREN, TR_CLOSED_AT_POP, TR_OPEN, TR_PROBED = 1, 2, 4, 8, 16
+
+
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
     global _lib
@@ -242,7 +257,8 @@ def lib():
             'simple_mip_solver_amd has no CPU fallback.')
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_SPILL_SIGNATURES.items()) +
-                                      list(_CUTMIG_SIGNATURES.items()) + list(_DUALFN_SIGNATURES.items())):
+                                      list(_CUTMIG_SIGNATURES.items()) + list(_DUALFN_SIGNATURES.items()) +
+                                      list(_TREEREC_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -939,6 +955,54 @@ class Tree:
         if got < 0:
             self.problem.ctx.check(int(got), 'mipx_tree_dual_records')
         return dict(node=node, parent=parent, status=status, t=tval, y=y)
+
+    def set_tree_record(self, on=True):
+        """Keep one record per node the search creates, from the first step on (mipx_tree_set_tree_record,
+        include/mipx_treerec.h)."""
+        self.problem.ctx.check(lib().mipx_tree_set_tree_record(self._h, int(bool(on))), 'mipx_tree_set_tree_record')
+
+    def tree_records(self, first=0, count=None):
+        """dict(parent, bvar, bdir, bval, depth, lp_status, flags, dual_bound, objective) of the records
+        [first, first + count), by default all of them (mipx_tree_records)."""
+        if count is None:
+            count = max(self.tree_record_stats()['nodes'] - int(first), 0)
+        count = int(count)
+        out = dict(parent=np.zeros(count, np.int64), bvar=np.zeros(count, np.int32), bdir=np.zeros(count, np.int32),
+                   bval=np.zeros(count), depth=np.zeros(count, np.int32), lp_status=np.zeros(count, np.int32),
+                   flags=np.zeros(count, np.int32), dual_bound=np.zeros(count), objective=np.zeros(count))
+        got = lib().mipx_tree_records(self._h, int(first), count, *(_ptr(a) for a in out.values()))
+        if got < 0:
+            self.problem.ctx.check(int(got), 'mipx_tree_records')
+        return {k: a[:got] for k, a in out.items()}
+
+    def node_bounds(self, ids):
+        """(l, u), len(ids) x n: the bounds of the recorded nodes `ids`, rebuilt on the device from the root's
+        bounds and the branchings of each node's lineage (mipx_tree_node_bounds)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        l = np.zeros((len(ids), self.problem.n)); u = np.zeros((len(ids), self.problem.n))
+        self.problem.ctx.check(lib().mipx_tree_node_bounds(self._h, len(ids), _ptr(ids), _ptr(l), _ptr(u)),
+                               'mipx_tree_node_bounds')
+        return l, u
+
+    def node_solve(self, ids, want_x=True, want_vstat=True):
+        """dict(status, obj, x, vstat) of the LPs of the recorded nodes `ids`, re-solved in one batched launch
+        from the root's optimal basis (mipx_tree_node_solve)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        K, n, nv = len(ids), self.problem.n, self.problem.n + self.problem.m
+        status = np.zeros(K, np.int32); obj = np.zeros(K)
+        x = np.zeros((K, n)) if want_x else None
+        vstat = np.zeros((K, nv), np.int8) if want_vstat else None
+        self.problem.ctx.check(lib().mipx_tree_node_solve(self._h, K, _ptr(ids), _ptr(status), _ptr(obj), _ptr(x), _ptr(vstat)),
+                               'mipx_tree_node_solve')
+        return dict(status=status, obj=obj, x=x, vstat=vstat)
+
+    def tree_record_stats(self):
+        """dict(nodes, host_bytes, device_bytes, materialised, resolved, query_ms) (mipx_tree_record_stats)."""
+        out = np.zeros(6, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_record_stats(self._h, _ptr(out)), 'mipx_tree_record_stats')
+        d = dict(zip(TREEREC_STATS_KEYS, (int(v) for v in out)))
+        d['query_ms'] /= 1000.0
+        return d
 
     def set_cut_migration(self, rows):
         """Reserve the top `rows` rows of the cut store for the cut rows of nodes received from other ranks, so

@@ -124,7 +124,7 @@ class BranchAndBound(BaseAlgorithm):
     def __init__(self, model, Node=BaseNode, node_queue=None, node_limit=INF, mip_gap=.0001,
                  logging=False, max_run_time=INF, initial_primal_bound=INF, frontier_batch=None,
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
-                 host_spill=None, cut_migration=None, dual_function=None, **kwargs):
+                 host_spill=None, cut_migration=None, dual_function=None, tree_record=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -135,7 +135,8 @@ class BranchAndBound(BaseAlgorithm):
         classes and the default queue; frontier_batch=1 keeps the reference's exact node order.
         With gomory_cuts=True (the reference's default, base_node.py:365) every node runs the cut
         rounds of BaseNode._base_bound inside the engine (register-tile shapes: m + 64 <= 192 rows,
-        n <= 256; no dive then).  In this mode `tree` holds only the root (nodes live on the device).
+        n <= 256; no dive then).  In this mode `tree` holds only the root (nodes live on the device) unless
+        tree_record is on.
         comm (extension; needs frontier_batch): an _ffi.Comm shared by one process per GPU
         (simple_mip_solver_amd.parallel.init_comm).  Every rank builds the same BranchAndBound and
         calls solve(): after a replicated ramp-up the open nodes are sharded over the ranks, which
@@ -176,7 +177,16 @@ class BranchAndBound(BaseAlgorithm):
         search starts, an int at that many bytes; once the cap is reached the search goes on and later
         nodes get no term (their leaves use their ancestors' terms: a valid, weaker bound; counted as
         `dropped`, RuntimeWarning).  Every step is then finished on the host.  Counters:
-        `dual_function_stats`."""
+        `dual_function_stats`.
+        tree_record (extension; needs frontier_batch and gomory_cuts=False, not with comm; default None = off):
+        True makes the engine keep one record per node it creates (parent, branching, LP verdict and
+        objective: 14 bytes of host memory per node, include/mipx_treerec.h), and after every solve() `tree`
+        answers the reference's queries for the whole native search -- `in`, get_children, get_leaves,
+        get_disjunction, get_node_instances, subtree_dual_bound, and so CutGeneratingLP(bb, root_id).  Node
+        objects are built for the nodes a query returns, their bounds rebuilt on the GPU from the records;
+        get_node_instances also fills `solution` of the LP-feasible nodes it returns, by one batched re-solve
+        (`tree.fill_solutions(nodes)` does so for any list of nodes).  Every step is then finished on the
+        host.  Counters: `tree_record_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -212,6 +222,14 @@ class BranchAndBound(BaseAlgorithm):
             'dual_function needs gomory_cuts=False: the dual function does not cover nodes with cut rows'
         self._dual_function = dual_function
         self.dual_function_stats = None
+        assert tree_record is None or tree_record is True, 'tree_record is None or True'
+        assert tree_record is None or frontier_batch is not None, \
+            'tree_record needs frontier_batch (the Python loop keeps every node in its tree)'
+        assert tree_record is None or comm is None, 'tree_record cannot be combined with comm'
+        assert tree_record is None or kwargs.get('gomory_cuts', True) is False, \
+            'tree_record needs gomory_cuts=False: recorded nodes carry no cut rows'
+        self._tree_record = tree_record
+        self.tree_record_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -384,6 +402,8 @@ class BranchAndBound(BaseAlgorithm):
                 pos, plus = lp._row_index()   # (True: -1, half of the device memory free now)
                 self._native.set_dual_record(-1 if self._dual_function is True else self._dual_function,
                                              lp.nConstraints, pos, np.where(plus, 1.0, -1.0))
+            if self._tree_record:
+                self._native.set_tree_record(True)
         st = None
         if self._comm is not None and not self._sharded:
             from simple_mip_solver_amd.parallel import shard_and_attach
@@ -433,6 +453,12 @@ class BranchAndBound(BaseAlgorithm):
         self._kwargs['next_node_idx'] = st['created_nodes']
         if issubclass(self._Node, PseudoCostBranchNode):
             self._kwargs['pseudo_costs'] = self._native.pseudo_costs()
+        if self._tree_record:   # `tree` on the engine's records, the nodes already handed out brought up to date
+            from simple_mip_solver_amd.algorithms.recorded_tree import RecordedTree
+            if not isinstance(self.tree, RecordedTree):
+                self.tree = RecordedTree(self)
+            self.tree.refresh()
+            self.tree_record_stats = self._native.tree_record_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')

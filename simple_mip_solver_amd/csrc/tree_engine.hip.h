@@ -21,6 +21,7 @@
 #include "finish_kernels.hip.h"
 #include "cutmig_kernels.hip.h"
 #include "dualfn_kernels.hip.h"
+#include "treerec_kernels.hip.h"
 
 struct NodeRec {
     double key;          // queue key: dual bound (best first) or -depth (depth first)
@@ -335,6 +336,8 @@ struct DualFn {
     std::vector<double> hostA;           // A (m x n), read back once for the penalised LP
 };
 
+#include "treerec.hip.h"
+
 struct mipx_tree {
     mipx_problem *prob = nullptr;
     mipx_ctx *ctx = nullptr;
@@ -461,6 +464,7 @@ struct mipx_tree {
     std::vector<double> root_l, root_u;   // the root's bounds (compact records store the differences)
     HostSpill hs;
     DualFn df;
+    TreeRec tr;
     // cut migration (mipx_tree_set_cut_migration): the top cm_rows rows of the cut store take the cut rows
     // of nodes received from other ranks, filled in order by the migration code (host-side fill level)
     int64_t cm_rows = 0, cm_used = 0;
@@ -966,6 +970,7 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
         nd.slot = -1;  // (the row itself is released when the step is finished)
         if (!(nd.dual_bound < t->primal)) {
             t->closed_min = std::fmin(t->closed_min, nd.dual_bound);
+            if (t->tr.on) t->tr.closed(id);
             if (spilled(slot)) spill_release(t, slot);   // (its record is dropped, never reloaded)
             else t->free_slots.push_back(slot);
             return;
@@ -1646,12 +1651,13 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
     // (best first on the bucket queue: the pushes of the step are collected and queued together below)
     const bool defer_push = t->use_bq && t->search == 0;
     t->pend.clear();
-    const bool rec = t->df.on;
+    const bool rec = t->df.on, trec = t->tr.on;
     std::vector<DfEntry> df_recs, df_infs;   // (dual function: this step's solved and infeasible nodes)
     auto evaluate = [&](int64_t id, int pos, int32_t slot, int level, int depth, int32_t anchor, int &err) -> int64_t {
         t->evaluated++;
         if (rec && status[pos] == 0) df_recs.push_back({pos, slot, id});
         if (rec && status[pos] == 1) df_infs.push_back({pos, slot, id});
+        if (trec) t->tr.solved(id, status[pos], obj[pos], mipf[pos] != 0, nprobe[pos] > 0);
         const bool lp_feasible = status[pos] == 0 || status[pos] == 2;
         if (status[pos] == 2) t->unbounded = true;
         int branched_on = -1;
@@ -1694,6 +1700,7 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
                         t->df.parent.push_back(id); t->df.rec.push_back(-1); t->df.haschild.push_back(0);
                         t->df.haschild[(size_t)id] = 1;
                     }
+                    if (trec) t->tr.child(id);
                     if (take_dive && dir == ddir[pos]) {
                         dive_child = cid;  // already solved: never enters the queue
                     } else if (defer_push) {
@@ -1760,6 +1767,12 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
         const int arc = mipx_problem_set_anchor(t->prob, rootv.data());
         if (arc) return arc;
         t->anchor_set = true;
+    }
+    // tree record: the root's optimal basis codes, once (the warm start of mipx_tree_node_solve)
+    if (trec && !t->tr.have_root && ids[0] == 0 && status[0] == 0) {
+        t->tr.root_v.resize(nv);
+        if ((rc = tree_d2h(t, t->tr.root_v.data(), S.d_vout, (size_t)nv))) return rc;
+        t->tr.have_root = true;
     }
     // 5. children records on the device, then release the evaluated nodes' rows
     const int P = (int)S.br[0].pos.size();
@@ -2699,6 +2712,14 @@ void mipx_tree_destroy(mipx_tree *t) {
             if (S.df_e1) (void)hipEventDestroy(S.df_e1);
         }
     }
+    {
+        TreeRec &tr = t->tr;
+        void *dp[] = {tr.d_nodes, tr.d_root, tr.d_root_v, tr.d_ids, tr.d_l, tr.d_u, tr.d_solve};
+        for (void *q : dp)
+            if (q) (void)hipFree(q);
+        if (tr.e0) (void)hipEventDestroy(tr.e0);
+        if (tr.e1) (void)hipEventDestroy(tr.e1);
+    }
     if (t->h_pairs) (void)hipHostFree(t->h_pairs);
     if (t->h_pres) (void)hipHostFree(t->h_pres);
     if (t->h_tab) (void)hipHostFree(t->h_tab);
@@ -3126,6 +3147,7 @@ int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps) {
     if (c && (t->hs.cap > 0 || t->hs.on_host > 0))
         return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the host spill (mipx_tree_set_host_spill)");
     if (c && t->df.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the dual function (mipx_tree_set_dual_record)");
+    if (c && t->tr.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the tree record (mipx_tree_set_tree_record)");
     t->comm = c;
     t->x_every = c ? every_steps : 0;
     if (!c) return MIPX_OK;
@@ -3502,3 +3524,4 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 }  // extern "C"
 
 #include "dualfn_api.hip.h"
+#include "treerec_api.hip.h"
