@@ -532,5 +532,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_cutmig.h"  /* migration of nodes with their cut rows in cut-round mode */
 #include "mipx_dualfn.h"  /* the dual function of a frontier-engine search */
 #include "mipx_treerec.h" /* the search tree of a frontier-engine search, kept as records */
+#include "mipx_cglp.h"    /* disjunctive cuts from a recorded tree by batched leaf separation */
 
 #endif /* MIPX_H */

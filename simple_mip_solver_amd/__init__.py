@@ -13,8 +13,10 @@ from simple_mip_solver_amd.nodes.nodes import PseudoCostBranchDepthFirstSearchNo
     DisjunctiveCutBoundPseudoCostBranchNode
 from simple_mip_solver_amd.milp_instance import MILPInstance
 from simple_mip_solver_amd.lp import CyLPArray, DenseLP
+from simple_mip_solver_amd.utils.disjunctive_separation import DisjunctiveSeparator
 
 __version__ = '0.1.0'
 __all__ = ['BaseNode', 'BranchAndBound', 'DepthFirstSearchNode', 'PseudoCostBranchNode',
            'PseudoCostBranchDepthFirstSearchNode', 'DisjunctiveCutBoundNode',
-           'DisjunctiveCutBoundPseudoCostBranchNode', 'MILPInstance', 'CyLPArray', 'DenseLP']
+           'DisjunctiveCutBoundPseudoCostBranchNode', 'MILPInstance', 'CyLPArray', 'DenseLP',
+           'DisjunctiveSeparator']

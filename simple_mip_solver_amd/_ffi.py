@@ -4,6 +4,7 @@ The library is built in-tree by `make -C simple_mip_solver_amd/csrc` (see __graf
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -244,6 +245,21 @@ TREEREC_STATS_KEYS = ('nodes', 'host_bytes', 'device_bytes', 'materialised', 're
 # flags of a record (MIPX_TR_* of the header)
 TR_MIP_FEASIBLE, TR_HAS_CHILDREN, TR_CLOSED_AT_POP, TR_OPEN, TR_PROBED = 1, 2, 4, 8, 16
 
+# ... and those of include/mipx_cglp.h (disjunctive cuts by batched leaf separation), which mipx.h includes
+# (tests/test_cglp_abi.py checks them against that header)
+_CGLP_SIGNATURES = {
+    'mipx_tree_support_open': (_i, [_vp, _vp, _i64, _vp]),
+    'mipx_tree_support_eval': (_i, [_vp, _vp, _d, _d, _i, _vp, _vp]),
+    'mipx_tree_support_leaves': (_i64, [_vp, _i, _i64, _vp]),
+    'mipx_tree_support_stats': (_i, [_vp, _vp]),
+    'mipx_tree_support_close': (None, [_vp]),
+}
+CGLP_SYMBOLS = list(_CGLP_SIGNATURES)
+CGLP_STATS_KEYS = ('leaves', 'dropped', 'evaluations', 'leaf_lps', 'iterations', 'pivots', 'device_bytes', 'kernel_ms',
+                   'select_ms')
+CGLP_HEAD = 8          # doubles in front of the rows of an evaluation's output block
+CGLP_MAX_POINTS = 1024
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -258,7 +274,7 @@ def lib():
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_SPILL_SIGNATURES.items()) +
                                       list(_CUTMIG_SIGNATURES.items()) + list(_DUALFN_SIGNATURES.items()) +
-                                      list(_TREEREC_SIGNATURES.items())):
+                                      list(_TREEREC_SIGNATURES.items()) + list(_CGLP_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -1004,6 +1020,13 @@ class Tree:
         d['query_ms'] /= 1000.0
         return d
 
+    def support_open(self, ids):
+        """A Support session on the recorded nodes `ids`, the terms of a disjunction (mipx_tree_support_open,
+        include/mipx_cglp.h).  It is closed with the tree at the latest."""
+        s = Support(self, ids)
+        self._sessions = [r for r in getattr(self, '_sessions', []) if r() is not None] + [weakref.ref(s)]
+        return s
+
     def set_cut_migration(self, rows):
         """Reserve the top `rows` rows of the cut store for the cut rows of nodes received from other ranks, so
         that open nodes can migrate in cut-round mode (mipx_tree_set_cut_migration, include/mipx_cutmig.h;
@@ -1087,8 +1110,76 @@ class Tree:
         return pi, pi0
 
     def close(self):
+        for ref in getattr(self, '_sessions', []):   # (a session's buffers belong to the tree's context)
+            if ref() is not None:
+                ref().close()
+        self._sessions = []
         if getattr(self, '_h', None) and getattr(self.problem, '_h', None):
             lib().mipx_tree_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Support:
+    """The leaves of a disjunction resident on the device, and their support values for a cut direction
+    (mipx_support, include/mipx_cglp.h)."""
+
+    def __init__(self, tree, ids):
+        self.tree = tree
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        h = _vp()
+        tree.problem.ctx.check(lib().mipx_tree_support_open(tree._h, _ptr(ids), len(ids), C.byref(h)),
+                               'mipx_tree_support_open')
+        self._h = h
+
+    def eval(self, pi, pi0, tol=0.0, max_points=1, want_margins=False):
+        """dict(min_margin, min_id, below, not_optimal, iterations, pivots, leaves, ids, h, x[, margins]): h_t(pi) of
+        every leaf against pi0 and the (at most max_points) leaves of smallest margin h_t - pi0, in ascending
+        order of (margin, node id), with a minimiser x of each (mipx_tree_support_eval)."""
+        n = self.tree.problem.n
+        pi = np.ascontiguousarray(pi, np.float64).reshape(n)
+        P = int(max_points)
+        block = np.zeros(CGLP_HEAD + P * (n + 2))
+        margins = np.zeros(self.leaves_count()) if want_margins else None
+        self.tree.problem.ctx.check(lib().mipx_tree_support_eval(self._h, _ptr(pi), float(pi0), float(tol), P, _ptr(block),
+                                                                 _ptr(margins)), 'mipx_tree_support_eval')
+        k = int(block[3])
+        rows = block[CGLP_HEAD:CGLP_HEAD + k * (n + 2)].reshape(k, n + 2)
+        out = dict(min_margin=float(block[0]), min_id=int(block[1]), below=int(block[2]), not_optimal=int(block[4]),
+                   iterations=int(block[5]), pivots=int(block[6]), leaves=int(block[7]),
+                   ids=rows[:, 0].astype(np.int64), h=rows[:, 1].copy(), x=rows[:, 2:].copy())
+        if want_margins:
+            out['margins'] = margins[:out['leaves']]
+        return out
+
+    def leaves_count(self):
+        return int(lib().mipx_tree_support_leaves(self._h, 0, 0, None))
+
+    def leaves(self, dropped=False):
+        """Node ids of the session's leaves, or of those dropped as infeasible (mipx_tree_support_leaves)."""
+        k = int(lib().mipx_tree_support_leaves(self._h, int(bool(dropped)), 0, None))
+        ids = np.zeros(max(k, 0), np.int64)
+        lib().mipx_tree_support_leaves(self._h, int(bool(dropped)), k, _ptr(ids))
+        return ids
+
+    def stats(self):
+        """dict(leaves, dropped, evaluations, leaf_lps, iterations, pivots, device_bytes, kernel_ms, select_ms)
+        (mipx_tree_support_stats)."""
+        out = np.zeros(9, np.int64)
+        self.tree.problem.ctx.check(lib().mipx_tree_support_stats(self._h, _ptr(out)), 'mipx_tree_support_stats')
+        d = dict(zip(CGLP_STATS_KEYS, (int(v) for v in out)))
+        d['kernel_ms'] /= 1000.0
+        d['select_ms'] /= 1000.0
+        return d
+
+    def close(self):
+        if getattr(self, '_h', None) and getattr(self.tree, '_h', None):
+            lib().mipx_tree_support_close(self._h)
         self._h = None
 
     def __del__(self):

@@ -22,6 +22,7 @@
 #include "cutmig_kernels.hip.h"
 #include "dualfn_kernels.hip.h"
 #include "treerec_kernels.hip.h"
+#include "cglp_kernels.hip.h"
 
 struct NodeRec {
     double key;          // queue key: dual bound (best first) or -depth (depth first)
@@ -3525,3 +3526,4 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 
 #include "dualfn_api.hip.h"
 #include "treerec_api.hip.h"
+#include "cglp_api.hip.h"
