@@ -533,5 +533,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_dualfn.h"  /* the dual function of a frontier-engine search */
 #include "mipx_treerec.h" /* the search tree of a frontier-engine search, kept as records */
 #include "mipx_cglp.h"    /* disjunctive cuts from a recorded tree by batched leaf separation */
+#include "mipx_restart.h" /* restart a recorded search at another right-hand side from its leaves */
 
 #endif /* MIPX_H */

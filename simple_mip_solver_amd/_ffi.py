@@ -260,6 +260,17 @@ CGLP_STATS_KEYS = ('leaves', 'dropped', 'evaluations', 'leaf_lps', 'iterations',
 CGLP_HEAD = 8          # doubles in front of the rows of an evaluation's output block
 CGLP_MAX_POINTS = 1024
 
+# ... and those of include/mipx_restart.h (restart of a recorded search at another right-hand side), which
+# mipx.h includes (tests/test_restart_abi.py checks them against that header)
+_RESTART_SIGNATURES = {
+    'mipx_tree_create_restart': (_i, [_vp, _vp, _pvp]),
+    'mipx_tree_restart_stats': (_i, [_vp, _vp]),
+    'mipx_tree_restart_seeds': (_i64, [_vp, _i64, _vp]),
+}
+RESTART_SYMBOLS = list(_RESTART_SIGNATURES)
+RESTART_STATS_KEYS = ('skeleton', 'seeds', 'device_bytes', 'seed_ms', 'seeds_evaluated', 'seeds_infeasible',
+                      'seeds_integral')
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -274,7 +285,8 @@ def lib():
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_SPILL_SIGNATURES.items()) +
                                       list(_CUTMIG_SIGNATURES.items()) + list(_DUALFN_SIGNATURES.items()) +
-                                      list(_TREEREC_SIGNATURES.items()) + list(_CGLP_SIGNATURES.items())):
+                                      list(_TREEREC_SIGNATURES.items()) + list(_CGLP_SIGNATURES.items()) +
+                                      list(_RESTART_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -767,6 +779,36 @@ class Tree:
         self.cuts = cp is not None
         self._h = h
         self.max_batch = int(max_batch)
+
+    @classmethod
+    def restart(cls, src, problem):
+        """A tree on `problem` (same A, c and shape as src's, another b) that starts from src's recorded leaves
+        (mipx_tree_create_restart, include/mipx_restart.h): src's creation parameters, pseudo-cost table and
+        root basis, its records as the skeleton, its childless records as the open nodes."""
+        h = _vp()
+        rc = lib().mipx_tree_create_restart(src._h, problem._h, C.byref(h))
+        problem.ctx.check(rc, 'mipx_tree_create_restart')
+        self = cls.__new__(cls)
+        self.problem, self.cuts, self._h, self.max_batch = problem, False, h, src.max_batch
+        return self
+
+    def restart_stats(self):
+        """dict(skeleton, seeds, device_bytes, seed_ms, seeds_evaluated, seeds_infeasible, seeds_integral)
+        (mipx_tree_restart_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_restart_stats(self._h, _ptr(out)), 'mipx_tree_restart_stats')
+        d = dict(zip(RESTART_STATS_KEYS, (int(v) for v in out)))
+        d['seed_ms'] /= 1000.0
+        return d
+
+    def restart_seeds(self):
+        """The ids of the seeds, ascending (mipx_tree_restart_seeds)."""
+        S = lib().mipx_tree_restart_seeds(self._h, 0, None)
+        if S < 0:
+            self.problem.ctx.check(int(S), 'mipx_tree_restart_seeds')
+        ids = np.zeros(S, np.int64)
+        lib().mipx_tree_restart_seeds(self._h, S, _ptr(ids))
+        return ids
 
     def solve(self, node_limit=0, mip_gap=1e-4, max_seconds=0.0, frontier_batch=None, max_steps=0):
         st = TreeStats()

@@ -193,6 +193,12 @@ class BranchAndBound(BaseAlgorithm):
             'lp_batch batches the Python loop; it cannot be combined with frontier_batch'
         assert lp_batch is None or comm is None, \
             'lp_batch runs on one GPU; it cannot be combined with comm'
+        # what restart() hands to the search it makes: the options as given, the node kwargs before any call
+        self._given = dict(node_limit=node_limit, mip_gap=mip_gap, logging=logging, max_run_time=max_run_time,
+                           frontier_batch=frontier_batch, pool_capacity=pool_capacity, anchor=anchor, dive=dive,
+                           host_spill=host_spill, tree_record=tree_record)
+        self._given_kwargs = dict(kwargs)
+        self.restart_stats = None
         self.lp_batch = lp_batch
         self.lp_batch_stats = None if lp_batch is None else \
             dict(launches=0, prefetched=0, consumed=0, wasted=0)
@@ -459,11 +465,77 @@ class BranchAndBound(BaseAlgorithm):
                 self.tree = RecordedTree(self)
             self.tree.refresh()
             self.tree_record_stats = self._native.tree_record_stats()
+        if self.restart_stats is not None:
+            self.restart_stats = self._native.restart_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')
             for key, value in totals.items():
                 self._kwargs[key] = self._native_totals0.get(key, 0) + value
+
+    _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive')
+
+    def restart(self, b, **overrides):
+        """A new, unsolved BranchAndBound for the same A, c, bounds and integer indices at the right-hand side
+        b, whose native search starts from the leaves of this one (include/mipx_restart.h): this search's records
+        are its skeleton, every childless node an open node with its bounds rebuilt on the GPU, warm-started
+        from the root's basis; the pseudo-cost table is carried over.  The childless nodes partition the integer
+        points of the root box at every b, so the restarted search is exact.  b follows the convention of
+        find_parameterized_dual_bound (a CyLPArray of the constraint's shape, negated with the same warning if
+        the constraints were flipped at instantiation).  Same Node class and keyword options; overrides may
+        change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor and dive.
+        Needs frontier_batch and tree_record=True and a solve() before; not with comm; the restarted search
+        records no dual function.  `restart_stats` of the new search reports the seeding."""
+        assert self.frontier_batch is not None and self._tree_record, \
+            'restart needs a search run with frontier_batch and tree_record=True'
+        assert self.status != 'unsolved', 'must solve this instance before using this method'
+        assert self._comm is None and 'comm' not in overrides, 'restart cannot be combined with comm'
+        assert not overrides.get('dual_function'), \
+            'dual_function is not available for a restarted search: the dual function keeps its own tree'
+        unknown = set(overrides) - set(self._restart_overrides) - {'dual_function'}
+        assert not unknown, f'restart overrides are {self._restart_overrides}, not {sorted(unknown)}'
+        assert isinstance(b, CyLPArray), 'this function only works with CyLP arrays'
+        lp = self.root_node.lp
+        assert len(lp.constraints) == 1 and b.shape == lp.constraints[0].lower.shape, \
+            'the shape of the RHS being added should match that of each node'
+        opts = dict(self._given)
+        opts.update({k: v for k, v in overrides.items() if k != 'dual_function'})
+        assert isinstance(opts['frontier_batch'], int) and 0 < opts['frontier_batch'] <= self.frontier_batch, \
+            'a restarted search steps with at most the frontier_batch of its source'
+        if self._swapped_constraint_direction:
+            b = -b
+            print('WARNING: your rhs was made negative to reflect constraints'
+                  ' flipping direction at instantiation')
+        from simple_mip_solver_amd.milp_instance import MILPInstance
+        m = self.model   # (already min c'x, A x >= b: base_algorithm._convert_constraints_to_greq)
+        model = MILPInstance(A=np.asarray(m.A), b=np.asarray(b, dtype=np.float64), c=m.lp.objective, l=m.l, u=m.u,
+                             integerIndices=m.integerIndices, sense=['Min', '>='], numVars=m.numVars)
+        kwargs = dict(self._given_kwargs)
+        if 'pseudo_costs' in kwargs:
+            kwargs['pseudo_costs'] = {}   # (the engine carries its table over)
+        new = BranchAndBound(model, self._Node, **opts, **kwargs)
+        new._swapped_constraint_direction = self._swapped_constraint_direction   # (b of a further restart: as here)
+        new._seed_native(self)
+        return new
+
+    def _seed_native(self, source):
+        """The native tree of a restarted search: made from the source's, not from the root."""
+        from simple_mip_solver_amd import _ffi
+        from simple_mip_solver_amd.lp import get_backend, HipBackend
+        backend = get_backend()
+        assert isinstance(backend, HipBackend), 'frontier_batch needs the HIP backend'
+        rs = self.root_node.lp._engine_form()
+        problem = backend._problem(rs.A, rs.b, rs.c, rs.key)
+        self._native_totals0 = {k: self._kwargs.get(k, 0) for k in _ffi.CUT_TOTAL_KEYS}
+        self._native = _ffi.Tree.restart(source._native, problem)
+        if self._anchor:
+            self._native.set_anchor_mode(True)
+        if self._dive:
+            self._native.set_dive(self._dive)
+        if self._host_spill:
+            self._native.set_host_spill(self._host_spill)
+        self.restart_stats = self._native.restart_stats()
+        self._kwargs['next_node_idx'] = source._kwargs['next_node_idx']
 
     def _evaluate_node(self, node):
         """Bound the node unless its inherited bound already prunes it; record an incumbent or

@@ -12,6 +12,7 @@ int mipx_tree_set_dual_record(mipx_tree *t, int64_t max_bytes, int rows, const i
         max_bytes = (int64_t)(free_b / 2);
     }
     if (max_bytes <= 0) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_dual_record: the byte cap must be positive (or -1)");
+    if (t->rs.on) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_dual_record: not on a restarted tree (mipx_tree_create_restart)");
     if (t->steps > 0 || t->nodes.size() != 1 || t->evaluated > 0)
         return fail(ctx, MIPX_EINVAL, "mipx_tree_set_dual_record: recording must be turned on before the first step");
     if (t->comm) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_dual_record: not with a communicator");

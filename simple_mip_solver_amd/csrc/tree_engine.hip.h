@@ -22,6 +22,7 @@
 #include "cutmig_kernels.hip.h"
 #include "dualfn_kernels.hip.h"
 #include "treerec_kernels.hip.h"
+#include "restart_kernels.hip.h"
 #include "cglp_kernels.hip.h"
 
 struct NodeRec {
@@ -116,7 +117,7 @@ struct BucketQueue {
         return r >= (double)(kMaxBuckets - 1) ? kMaxBuckets - 1 : (size_t)r;
     }
     void push(double key, int64_t id) {
-        if (!started && std::isfinite(key)) {  // (the root's inherited bound is -inf: bucket 0)
+        if (!started && !hold && std::isfinite(key)) {  // (the root's inherited bound is -inf: bucket 0)
             started = true;
             k0 = key;
             inv_width = 4096.0 / std::fmax(std::fabs(key), 1.0);  // bucket width: 2^-12 of |first key|
@@ -164,8 +165,33 @@ struct BucketQueue {
         for (const Item &it : tab[cur]) k = std::fmin(k, it.key);
         return k;
     }
+    // Restart (mipx_restart.h): the seeds are keyed -inf and their children's keys come in no order, so the
+    // first finite key is not the smallest.  While a seed is in the queue there is no scale -- everything
+    // lies in bucket 0, split exactly by pop_batch -- and the scale is set from the smallest key once the
+    // last seed has left.
+    bool hold = false;
+    void release_hold() {
+        const double inf = std::numeric_limits<double>::infinity();
+        if (tab.empty()) return;
+        double mn = inf;
+        for (const Item &it : tab[0]) {
+            if (it.key == -inf) return;   // (a seed is still there)
+            mn = std::fmin(mn, it.key);
+        }
+        if (!std::isfinite(mn)) return;
+        hold = false;
+        std::vector<Item> all;
+        all.swap(tab[0]);
+        count = 0;
+        cur = 0;
+        started = true;   // the scale push() would take from a first key, from the smallest one
+        k0 = mn;
+        inv_width = 4096.0 / std::fmax(std::fabs(mn), 1.0);
+        for (const Item &it : all) push(it.key, it.id);
+    }
     // the `want` smallest items (ties: smaller id first) are appended to out
     void pop_batch(size_t want, std::vector<Item> &out) {
+        if (hold) release_hold();
         while (want > 0 && count > 0) {
             settle();
             std::vector<Item> &v = tab[cur];
@@ -174,7 +200,8 @@ struct BucketQueue {
                 want -= v.size();
                 count -= v.size();
                 v.clear();
-            } else if (v.size() > 8 * want && tab.size() * 16 < kMaxBuckets && refinements < max_refinements) {
+            } else if (started && v.size() > 8 * want && tab.size() * 16 < kMaxBuckets && refinements < max_refinements) {
+                // (before the first finite key there is no scale to refine: the seeds of a restart, all keyed -inf)
                 // a deep search piles its open nodes just above the dual bound: buckets sized for
                 // the first key end up holding 10^5..10^6 of them and every step pays nth_element
                 // and an erase over all of those (2.7 ms per step at 5 M open nodes) -> finer buckets
@@ -339,6 +366,15 @@ struct DualFn {
 
 #include "treerec.hip.h"
 
+// Restart (include/mipx_restart.h): what a tree made by mipx_tree_create_restart knows of its making.
+struct RestartRec {
+    bool on = false;
+    int64_t skeleton = 0;             // records copied from the source
+    std::vector<int64_t> seeds;       // the source's childless records, ascending: the open nodes it started with
+    int64_t bytes = 0;                // device bytes the seeding wrote
+    double seed_us = 0.0;             // device time of restart_seed
+};
+
 struct mipx_tree {
     mipx_problem *prob = nullptr;
     mipx_ctx *ctx = nullptr;
@@ -466,6 +502,7 @@ struct mipx_tree {
     HostSpill hs;
     DualFn df;
     TreeRec tr;
+    RestartRec rs;
     // cut migration (mipx_tree_set_cut_migration): the top cm_rows rows of the cut store take the cut rows
     // of nodes received from other ranks, filled in order by the migration code (host-side fill level)
     int64_t cm_rows = 0, cm_used = 0;
@@ -1098,7 +1135,7 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
         }
         HIP_TRY(ctx, hipEventRecord(S.e0, st));
         t->cold_launch = B == 1 && t->nodes.size() == 1 && S.recs[0].depth == 0 && S.recs[0].b_idx == -1 && S.recs[0].ncut == 0 &&
-                         !t->prob->anchor_on;   // (the root alone, never solved, no cut yet: one cold LP)
+                         !t->prob->anchor_on && !t->rs.on;   // (the root alone, never solved, no cut yet: one cold LP)
         rc = launch_lp(t, B, t->pool_l, t->pool_u, t->pool_v, S.d_slot, 0, S.d_status, S.d_obj, S.d_x,
                        S.d_vout, S.d_iters, S.d_npiv, nullptr, nullptr, S.d_slot + B, &cl);
         if (rc) return rc;
@@ -1109,7 +1146,8 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
     }
     HIP_TRY(ctx, hipEventRecord(S.e0, st));
     // the root alone, never solved: one cold LP (above the register tiles it is spread over the chip, K1c)
-    t->cold_launch = B == 1 && t->nodes.size() == 1 && S.recs[0].depth == 0 && S.recs[0].b_idx == -1 && !t->prob->anchor_on;
+    t->cold_launch = B == 1 && t->nodes.size() == 1 && S.recs[0].depth == 0 && S.recs[0].b_idx == -1 && !t->prob->anchor_on &&
+                     !t->rs.on;   // (a restart's root is a seed: its row holds the source's root basis)
     rc = launch_lp(t, B, t->pool_l, t->pool_u, t->pool_v, S.d_slot, 0, S.d_status, S.d_obj,
                    S.d_x, S.d_vout, S.d_iters, S.d_npiv, nullptr, S.dive ? &S : nullptr, S.d_slot + B, nullptr,
                    t->df.on ? S.df_y : nullptr);
@@ -1560,7 +1598,8 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
                     if (var == nd.b_idx) own_probed = true;
                     changed = true;
                 }
-                if (nd.b_idx >= 0 && !own_probed) {
+                // (a seed of a restart inherits no bound: its parent was not solved at this right-hand side)
+                if (nd.b_idx >= 0 && !own_probed && !(t->rs.on && nd.dual_bound == -inf)) {
                     // variable_change: b_val - u[b_idx] (left) or l[b_idx] - b_val (right)
                     const double vc = nd.b_dir == 0 ? nd.b_val - std::floor(nd.b_val)
                                                     : std::ceil(nd.b_val) - nd.b_val;
@@ -2812,6 +2851,12 @@ int mipx_tree_solve(mipx_tree *t, int64_t node_limit, double mip_gap, double max
         t->started = true;
         tree_push(t, 0);
     }
+    if (t->rs.on && t->anchor_mode && !t->anchor_set && t->tr.have_root && t->steps == 0) {
+        // restart: the seeds warm-start from the source's root basis, and its tableau at this b is the anchor
+        const int arc = mipx_problem_set_anchor(t->prob, t->tr.root_v.data());
+        if (arc) return arc;
+        t->anchor_set = true;
+    }
     int64_t steps = 0, hooked_at = 0, xchg_at = 0;
     bool hook_stop = false;
     if (t->comm) {
@@ -3527,3 +3572,4 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "dualfn_api.hip.h"
 #include "treerec_api.hip.h"
 #include "cglp_api.hip.h"
+#include "restart_api.hip.h"

@@ -33,6 +33,26 @@ struct TrBoundsArgs {
     int8_t *out_v = nullptr;          // count x nv
 };
 
+// The walk of node `id`'s lineage over rows lo / up that hold the root's bounds, `seen` zeroed: thread tid acts
+// on the columns j with j % kTrNT == tid only (it must be the thread that initialised them).  Shared by
+// treerec_bounds and restart_seed (restart_kernels.hip.h), so that the two write the same bits.
+__device__ __forceinline__ void tr_apply_lineage(const TrNode *nodes, int64_t nodes_count, int64_t id, int n, int tid,
+                                                 double *lo, double *up, uint8_t *seen) {
+    while (id > 0 && id < nodes_count) {   // (a parent's id is below its child's: the walk ends at 0)
+        const TrNode r = nodes[id];
+        const int var = r.vd >> 1, right = r.vd & 1;
+        if (var >= 0 && var < n && (var % kTrNT) == tid) {
+            const uint8_t bit = (uint8_t)(1 << right);
+            if (!(seen[var] & bit)) {
+                seen[var] |= bit;
+                if (right) lo[var] = ceil(r.val);
+                else up[var] = floor(r.val);
+            }
+        }
+        id = r.parent < id ? r.parent : -1;
+    }
+}
+
 __global__ void __launch_bounds__(kTrNT) treerec_bounds(TrBoundsArgs g) {
     extern __shared__ uint8_t tr_seen[];   // n bytes: bit 0 an upper bound, bit 1 a lower bound was set
     const int k = blockIdx.x;
@@ -46,20 +66,7 @@ __global__ void __launch_bounds__(kTrNT) treerec_bounds(TrBoundsArgs g) {
     }
     if (g.out_v != nullptr && g.root_v != nullptr)
         for (int j = tid; j < g.nv; j += kTrNT) g.out_v[(size_t)k * g.nv + j] = g.root_v[j];
-    int64_t id = g.ids[k];
-    while (id > 0 && id < g.nodes_count) {   // (a parent's id is below its child's: the walk ends at 0)
-        const TrNode r = g.nodes[id];
-        const int var = r.vd >> 1, right = r.vd & 1;
-        if (var >= 0 && var < n && (var % kTrNT) == tid) {
-            const uint8_t bit = (uint8_t)(1 << right);
-            if (!(tr_seen[var] & bit)) {
-                tr_seen[var] |= bit;
-                if (right) lo[var] = ceil(r.val);
-                else up[var] = floor(r.val);
-            }
-        }
-        id = r.parent < id ? r.parent : -1;
-    }
+    tr_apply_lineage(g.nodes, g.nodes_count, g.ids[k], n, tid, lo, up, tr_seen);
 }
 
 }  // namespace mipx
