@@ -271,6 +271,19 @@ RESTART_SYMBOLS = list(_RESTART_SIGNATURES)
 RESTART_STATS_KEYS = ('skeleton', 'seeds', 'device_bytes', 'seed_ms', 'seeds_evaluated', 'seeds_infeasible',
                       'seeds_integral')
 
+# ... and those of include/mipx_heur.h (the primal heuristic: round, repair and lift LP points), which mipx.h
+# includes (tests/test_heuristic_abi.py checks them against that header)
+_HEUR_SIGNATURES = {
+    'mipx_round_repair_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _d, _i] + [_vp] * 5),
+    'mipx_tree_set_heuristic': (_i, [_vp, _i, _i, _i]),
+    'mipx_tree_heuristic_stats': (_i, [_vp, _vp]),
+}
+HEUR_SYMBOLS = list(_HEUR_SIGNATURES)
+HEUR_STATS_KEYS = ('points', 'feasible', 'stuck', 'capped', 'repair_moves', 'lift_moves', 'incumbents', 'kernel_us')
+HEUR_STATUS = {0: 'feasible', 1: 'stuck', 2: 'capped', 3: 'skipped'}
+# points per step that primal_heuristic=True / set_heuristic(True) take
+DEFAULT_HEURISTIC_POINTS = 32
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -286,7 +299,7 @@ def lib():
     for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_SPILL_SIGNATURES.items()) +
                                       list(_CUTMIG_SIGNATURES.items()) + list(_DUALFN_SIGNATURES.items()) +
                                       list(_TREEREC_SIGNATURES.items()) + list(_CGLP_SIGNATURES.items()) +
-                                      list(_RESTART_SIGNATURES.items())):
+                                      list(_RESTART_SIGNATURES.items()) + list(_HEUR_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -730,6 +743,23 @@ class Problem:
         return [dict(row_idx=row_idx[k, :ncuts[k]], pi=pi[k, :ncuts[k]], pi0=pi0[k, :ncuts[k]],
                      safe_pi=spi[k, :ncuts[k]], safe_pi0=spi0[k, :ncuts[k]]) for k in range(B)]
 
+    def round_repair_batch(self, x, l, u, integer_indices, tol=1e-9, max_moves=None, skip=None):
+        """The primal heuristic on host buffers (mipx_round_repair_batch, include/mipx_heur.h): x (batch, n) points,
+        l, u the bounds (n each), skip an optional (batch,) mask.  Returns dict of x (batch, n), obj, status
+        (HEUR_STATUS codes) and moves (batch, 2: repair, lift); max_moves None: m + n."""
+        n = self.n
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n)
+        B = x.shape[0]
+        l, u = _arr(l, np.float64, n), _arr(u, np.float64, n)
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        sk = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8).reshape(B)
+        max_moves = self.m + n if max_moves is None else int(max_moves)
+        xo = np.zeros((B, n)); obj = np.zeros(B); status = np.zeros(B, np.int32); moves = np.zeros((B, 2), np.int32)
+        rc = lib().mipx_round_repair_batch(self._h, B, _ptr(x), _ptr(l), _ptr(u), _ptr(ii), len(ii), float(tol), max_moves,
+                                           _ptr(sk), _ptr(xo), _ptr(obj), _ptr(status), _ptr(moves))
+        self.ctx.check(rc, 'mipx_round_repair_batch')
+        return dict(x=xo, obj=obj, status=status, moves=moves)
+
     def solve_batch_dev(self, B, d_l, d_u, d_vstat, max_iter, d_status, d_obj, d_x, d_y, d_vout,
                         d_iters, d_npiv):
         rc = lib().mipx_lp_solve_batch_dev(self._h, int(B), d_l, d_u, d_vstat, int(max_iter),
@@ -1068,6 +1098,22 @@ class Tree:
         s = Support(self, ids)
         self._sessions = [r for r in getattr(self, '_sessions', []) if r() is not None] + [weakref.ref(s)]
         return s
+
+    def set_heuristic(self, points=True, every_steps=1, max_moves=None):
+        """Round, repair and lift the node LP solutions of the first `points` nodes of every `every_steps`-th step on
+        the GPU and take the best feasible point as the incumbent where it beats the one the tree holds
+        (mipx_tree_set_heuristic, include/mipx_heur.h; True: DEFAULT_HEURISTIC_POINTS; max_moves None: m + n)."""
+        points = DEFAULT_HEURISTIC_POINTS if points is True else int(points)
+        max_moves = self.problem.m + self.problem.n if max_moves is None else int(max_moves)
+        self.problem.ctx.check(lib().mipx_tree_set_heuristic(self._h, points, int(every_steps), max_moves),
+                               'mipx_tree_set_heuristic')
+
+    def heuristic_stats(self):
+        """dict(points, feasible, stuck, capped, repair_moves, lift_moves, incumbents, kernel_us)
+        (mipx_tree_heuristic_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_heuristic_stats(self._h, _ptr(out)), 'mipx_tree_heuristic_stats')
+        return dict(zip(HEUR_STATS_KEYS, (int(v) for v in out)))
 
     def set_cut_migration(self, rows):
         """Reserve the top `rows` rows of the cut store for the cut rows of nodes received from other ranks, so

@@ -124,7 +124,8 @@ class BranchAndBound(BaseAlgorithm):
     def __init__(self, model, Node=BaseNode, node_queue=None, node_limit=INF, mip_gap=.0001,
                  logging=False, max_run_time=INF, initial_primal_bound=INF, frontier_batch=None,
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
-                 host_spill=None, cut_migration=None, dual_function=None, tree_record=None, **kwargs):
+                 host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
+                 **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -186,7 +187,14 @@ class BranchAndBound(BaseAlgorithm):
         objects are built for the nodes a query returns, their bounds rebuilt on the GPU from the records;
         get_node_instances also fills `solution` of the LP-feasible nodes it returns, by one batched re-solve
         (`tree.fill_solutions(nodes)` does so for any list of nodes).  Every step is then finished on the
-        host.  Counters: `tree_record_stats`."""
+        host.  Counters: `tree_record_stats`.
+        primal_heuristic (extension; needs frontier_batch and gomory_cuts=False, not with comm; default None = off):
+        after the node LPs of every step the engine rounds the LP solutions of the step's first nodes to integers,
+        repairs the rows the rounding broke by unit moves and lifts the objective by unit moves that keep every
+        row, one GPU workgroup per point (include/mipx_heur.h); the best feasible point becomes the incumbent
+        where it beats the one the search holds, before the step's nodes are pruned against it.  True takes 32
+        points per step, an int that many; at most m + n moves per point.  The optimum is the same; the nodes
+        evaluated on the way differ.  Every step is then finished on the host.  Counters: `heuristic_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -196,7 +204,7 @@ class BranchAndBound(BaseAlgorithm):
         # what restart() hands to the search it makes: the options as given, the node kwargs before any call
         self._given = dict(node_limit=node_limit, mip_gap=mip_gap, logging=logging, max_run_time=max_run_time,
                            frontier_batch=frontier_batch, pool_capacity=pool_capacity, anchor=anchor, dive=dive,
-                           host_spill=host_spill, tree_record=tree_record)
+                           host_spill=host_spill, tree_record=tree_record, primal_heuristic=primal_heuristic)
         self._given_kwargs = dict(kwargs)
         self.restart_stats = None
         self.lp_batch = lp_batch
@@ -236,6 +244,16 @@ class BranchAndBound(BaseAlgorithm):
             'tree_record needs gomory_cuts=False: recorded nodes carry no cut rows'
         self._tree_record = tree_record
         self.tree_record_stats = None
+        assert primal_heuristic is None or primal_heuristic is True or (
+            isinstance(primal_heuristic, int) and not isinstance(primal_heuristic, bool) and primal_heuristic > 0), \
+            'primal_heuristic is None, True or a positive number of points per step'
+        assert primal_heuristic is None or frontier_batch is not None, \
+            'primal_heuristic needs frontier_batch (it runs on the node LP solutions of the native engine)'
+        assert primal_heuristic is None or comm is None, 'primal_heuristic cannot be combined with comm'
+        assert primal_heuristic is None or kwargs.get('gomory_cuts', True) is False, \
+            'primal_heuristic needs gomory_cuts=False: the heuristic does not run on nodes with cut rows'
+        self._primal_heuristic = primal_heuristic
+        self.heuristic_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -410,6 +428,8 @@ class BranchAndBound(BaseAlgorithm):
                                              lp.nConstraints, pos, np.where(plus, 1.0, -1.0))
             if self._tree_record:
                 self._native.set_tree_record(True)
+            if self._primal_heuristic:
+                self._native.set_heuristic(self._primal_heuristic)
         st = None
         if self._comm is not None and not self._sharded:
             from simple_mip_solver_amd.parallel import shard_and_attach
@@ -467,13 +487,15 @@ class BranchAndBound(BaseAlgorithm):
             self.tree_record_stats = self._native.tree_record_stats()
         if self.restart_stats is not None:
             self.restart_stats = self._native.restart_stats()
+        if self._primal_heuristic:
+            self.heuristic_stats = self._native.heuristic_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')
             for key, value in totals.items():
                 self._kwargs[key] = self._native_totals0.get(key, 0) + value
 
-    _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive')
+    _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive', 'primal_heuristic')
 
     def restart(self, b, **overrides):
         """A new, unsolved BranchAndBound for the same A, c, bounds and integer indices at the right-hand side
@@ -483,7 +505,8 @@ class BranchAndBound(BaseAlgorithm):
         points of the root box at every b, so the restarted search is exact.  b follows the convention of
         find_parameterized_dual_bound (a CyLPArray of the constraint's shape, negated with the same warning if
         the constraints were flipped at instantiation).  Same Node class and keyword options; overrides may
-        change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor and dive.
+        change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor, dive and
+        primal_heuristic.
         Needs frontier_batch and tree_record=True and a solve() before; not with comm; the restarted search
         records no dual function.  `restart_stats` of the new search reports the seeding."""
         assert self.frontier_batch is not None and self._tree_record, \
@@ -534,6 +557,8 @@ class BranchAndBound(BaseAlgorithm):
             self._native.set_dive(self._dive)
         if self._host_spill:
             self._native.set_host_spill(self._host_spill)
+        if self._primal_heuristic:
+            self._native.set_heuristic(self._primal_heuristic)
         self.restart_stats = self._native.restart_stats()
         self._kwargs['next_node_idx'] = source._kwargs['next_node_idx']
 

@@ -23,6 +23,7 @@
 #include "dualfn_kernels.hip.h"
 #include "treerec_kernels.hip.h"
 #include "restart_kernels.hip.h"
+#include "heur_kernels.hip.h"
 #include "cglp_kernels.hip.h"
 
 struct NodeRec {
@@ -304,6 +305,7 @@ struct StepBuf {
     char *df_h = nullptr, *df_d = nullptr;
     hipEvent_t df_e0 = nullptr, df_e1 = nullptr;
     bool df_timed = false;
+    int heur_n = 0;   // primal heuristic: the points of this step it was launched on (0: none)
     int B = 0;
     bool in_flight = false;
     double inflight_min = std::numeric_limits<double>::infinity();   // lowest inherited bound of the batch (exchange record)
@@ -373,6 +375,21 @@ struct RestartRec {
     std::vector<int64_t> seeds;       // the source's childless records, ascending: the open nodes it started with
     int64_t bytes = 0;                // device bytes the seeding wrote
     double seed_us = 0.0;             // device time of restart_seed
+};
+
+// Primal heuristic (include/mipx_heur.h): the option's parameters, the root's bounds on the device, and per step
+// buffer the rounded points and what comes down with each step: [obj (P f64) | status (P i32) | moves (2 P i32)].
+struct HeurState {
+    bool on = false;
+    int points = 0, every = 1, max_moves = 0;
+    int cap = 0;                     // points the step buffers are laid out for
+    double tol = 1e-9;
+    double *d_lu = nullptr;          // [root l | root u]
+    double *d_x[3] = {nullptr, nullptr, nullptr};
+    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    int64_t tried = 0, feasible = 0, stuck = 0, capped = 0, repair = 0, lift = 0, installed = 0;
+    double us = 0.0;                 // device time of heur_round_repair
 };
 
 struct mipx_tree {
@@ -503,6 +520,7 @@ struct mipx_tree {
     DualFn df;
     TreeRec tr;
     RestartRec rs;
+    HeurState hr;
     // cut migration (mipx_tree_set_cut_migration): the top cm_rows rows of the cut store take the cut rows
     // of nodes received from other ranks, filled in order by the migration code (host-side fill level)
     int64_t cm_rows = 0, cm_used = 0;
@@ -638,6 +656,79 @@ int launch_lp(mipx_tree *t, int batch, const double *l, const double *u, const i
 int tree_d2h(mipx_tree *t, void *dst, const void *src, size_t bytes) {
     HIP_TRY(t->ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, t->st2));
     HIP_TRY(t->ctx, hipStreamSynchronize(t->st2));
+    return MIPX_OK;
+}
+
+// ---- primal heuristic (include/mipx_heur.h) ---------------------------------------------------------------
+// One launch of heur_round_repair over `batch` points in device memory, queued on `st`.
+int heur_launch(const mipx_problem *p, hipStream_t st, int batch, const double *d_x, const double *d_l, const double *d_u,
+                const int32_t *d_int_idx, int n_int, double tol, int max_moves, const uint8_t *d_skip,
+                const int32_t *d_lp_status, double *d_x_out, double *d_obj, int32_t *d_status, int32_t *d_moves) {
+    mipx_ctx *ctx = p->ctx;
+    if (p->m > mipx::kHeurMax || p->n > mipx::kHeurMax) return fail(ctx, MIPX_ETOOBIG, "primal heuristic: more than 1024 rows or columns");
+    if (batch <= 0) return MIPX_OK;
+    mipx::HeurArgs a;
+    a.m = p->m; a.n = p->n; a.n_int = n_int; a.max_moves = max_moves; a.tol = tol;
+    a.A = p->dA; a.b = p->db; a.c = p->dc; a.l = d_l; a.u = d_u; a.int_idx = d_int_idx;
+    a.x = d_x; a.lp_status = d_lp_status; a.skip = d_skip;
+    a.x_out = d_x_out; a.obj_out = d_obj; a.status_out = d_status; a.moves_out = d_moves;
+    hipLaunchKernelGGL(mipx::heur_round_repair, dim3((unsigned)batch), dim3(mipx::kHeurNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
+// The step's node LP solutions (level 0, the first positions) through the heuristic, behind its node LPs.
+int heur_step_launch(mipx_tree *t, StepBuf &S) {
+    HeurState &hr = t->hr;
+    S.heur_n = 0;
+    if (!hr.on || t->steps % hr.every != 0) return MIPX_OK;
+    mipx_ctx *ctx = t->ctx;
+    hipStream_t st = ctx->stream;
+    const int bi = (int)(&S - t->buf), P = std::min(S.B, hr.points);
+    double *obj = (double *)hr.d_out[bi];
+    int32_t *status = (int32_t *)(obj + hr.cap), *moves = status + hr.cap;
+    HIP_TRY(ctx, hipEventRecord(hr.e0[bi], st));
+    const int rc = heur_launch(t->prob, st, P, S.d_x, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
+                               nullptr, S.d_status, hr.d_x[bi], obj, status, moves);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(hr.e1[bi], st));
+    S.heur_n = P;
+    return MIPX_OK;
+}
+
+// ... and what it found, before the step's nodes are evaluated: the best feasible point (ties: the lowest
+// position) is the incumbent if it beats the one the tree holds -- as an incumbent received from an exchange.
+int heur_step_collect(mipx_tree *t, StepBuf &S) {
+    HeurState &hr = t->hr;
+    const int bi = (int)(&S - t->buf), P = S.heur_n, n = t->n;
+    S.heur_n = 0;
+    int rc = tree_d2h(t, hr.h_out[bi], hr.d_out[bi], (size_t)hr.cap * 20);
+    if (rc) return rc;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, hr.e0[bi], hr.e1[bi]) == hipSuccess) hr.us += 1000.0 * ms;
+    const double *obj = (const double *)hr.h_out[bi];
+    const int32_t *status = (const int32_t *)(obj + hr.cap), *moves = status + hr.cap;
+    int best = -1;
+    for (int k = 0; k < P; k++) {
+        if (status[k] == MIPX_HEUR_SKIPPED) continue;
+        hr.tried++;
+        hr.repair += moves[2 * k];
+        hr.lift += moves[2 * k + 1];
+        if (status[k] == MIPX_HEUR_STUCK) hr.stuck++;
+        if (status[k] == MIPX_HEUR_CAPPED) hr.capped++;
+        if (status[k] != MIPX_HEUR_FEASIBLE) continue;
+        hr.feasible++;
+        if (best < 0 || obj[k] < obj[best]) best = k;
+    }
+    if (best >= 0 && obj[best] < t->primal) {
+        t->primal = obj[best];
+        if ((rc = tree_d2h(t, t->best_x.data(), hr.d_x[bi] + (size_t)best * n, (size_t)n * 8))) return rc;
+        t->have_x = true;
+        // (the point is a closed leaf of value obj: without it no closed leaf holds the incumbent's value, and the
+        // dual bound of an emptied queue would end above the incumbent instead of on it)
+        t->closed_min = std::fmin(t->closed_min, obj[best]);
+        hr.installed++;
+    }
     return MIPX_OK;
 }
 
@@ -1161,6 +1252,7 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
         return launch_finish(t, S);   // (records S.done behind the finish, on stf)
     }
     if ((rc = launch_score(t, S, (S.dive + 1) * B))) return rc;
+    if (t->hr.on && (rc = heur_step_launch(t, S))) return rc;
     HIP_TRY(ctx, hipEventRecord(S.done, st));
     return MIPX_OK;
 }
@@ -1443,6 +1535,7 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, S.e0, S.e1) == hipSuccess) t->kernel_ms += ms;
     }
+    if (S.heur_n > 0 && (rc = heur_step_collect(t, S))) return rc;   // (primal heuristic: its incumbent prunes this step's nodes)
     // The nodes this function finishes, in order.  The whole batch: the nodes without probe requests first,
     // then those with (each group in batch order) -- the order in which the device finish and the host part
     // below share a step, so that both ways end with the same table, ids and queue.  Device finish: only
@@ -2760,6 +2853,17 @@ void mipx_tree_destroy(mipx_tree *t) {
         if (tr.e0) (void)hipEventDestroy(tr.e0);
         if (tr.e1) (void)hipEventDestroy(tr.e1);
     }
+    {
+        HeurState &hr = t->hr;
+        if (hr.d_lu) (void)hipFree(hr.d_lu);
+        for (int k = 0; k < 3; k++) {
+            if (hr.d_x[k]) (void)hipFree(hr.d_x[k]);
+            if (hr.d_out[k]) (void)hipFree(hr.d_out[k]);
+            if (hr.h_out[k]) (void)hipHostFree(hr.h_out[k]);
+            if (hr.e0[k]) (void)hipEventDestroy(hr.e0[k]);
+            if (hr.e1[k]) (void)hipEventDestroy(hr.e1[k]);
+        }
+    }
     if (t->h_pairs) (void)hipHostFree(t->h_pairs);
     if (t->h_pres) (void)hipHostFree(t->h_pres);
     if (t->h_tab) (void)hipHostFree(t->h_tab);
@@ -3194,6 +3298,7 @@ int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps) {
         return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the host spill (mipx_tree_set_host_spill)");
     if (c && t->df.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the dual function (mipx_tree_set_dual_record)");
     if (c && t->tr.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the tree record (mipx_tree_set_tree_record)");
+    if (c && t->hr.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the primal heuristic (mipx_tree_set_heuristic)");
     t->comm = c;
     t->x_every = c ? every_steps : 0;
     if (!c) return MIPX_OK;
@@ -3573,3 +3678,4 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "treerec_api.hip.h"
 #include "cglp_api.hip.h"
 #include "restart_api.hip.h"
+#include "heur_api.hip.h"
