@@ -284,6 +284,20 @@ HEUR_STATUS = {0: 'feasible', 1: 'stuck', 2: 'capped', 3: 'skipped'}
 # points per step that primal_heuristic=True / set_heuristic(True) take
 DEFAULT_HEURISTIC_POINTS = 32
 
+# ... and those of include/mipx_prop.h (node presolve: activity-based bound propagation), which mipx.h includes
+# (tests/test_propagation_abi.py checks them against that header)
+_PROP_SIGNATURES = {
+    'mipx_propagate_batch': (_i, [_vp, _i] + [_vp] * 3 + [_i, _d, _d, _i] + [_vp] * 5),
+    'mipx_tree_set_propagation': (_i, [_vp, _i, _i]),
+    'mipx_tree_propagation_stats': (_i, [_vp, _vp]),
+}
+PROP_SYMBOLS = list(_PROP_SIGNATURES)
+PROP_STATS_KEYS = ('nodes', 'tightened', 'infeasible', 'bounds_changed', 'rounds', 'capped', 'reserved', 'kernel_us')
+PROP_STATUS = {0: 'unchanged', 1: 'tightened', 2: 'infeasible'}
+# rounds that propagate=True / set_propagation(True) take, and the tolerance of the engine's runs
+DEFAULT_PROPAGATION_ROUNDS = 8
+PROPAGATION_TOL = 1e-6
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -299,7 +313,8 @@ def lib():
     for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_SPILL_SIGNATURES.items()) +
                                       list(_CUTMIG_SIGNATURES.items()) + list(_DUALFN_SIGNATURES.items()) +
                                       list(_TREEREC_SIGNATURES.items()) + list(_CGLP_SIGNATURES.items()) +
-                                      list(_RESTART_SIGNATURES.items()) + list(_HEUR_SIGNATURES.items())):
+                                      list(_RESTART_SIGNATURES.items()) + list(_HEUR_SIGNATURES.items()) +
+                                      list(_PROP_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -760,6 +775,24 @@ class Problem:
         self.ctx.check(rc, 'mipx_round_repair_batch')
         return dict(x=xo, obj=obj, status=status, moves=moves)
 
+    def propagate_batch(self, l, u, integer_indices, cutoff=None, tol=PROPAGATION_TOL, max_rounds=DEFAULT_PROPAGATION_ROUNDS):
+        """Bound propagation on host buffers (mipx_propagate_batch, include/mipx_prop.h): l, u (batch, n) boxes,
+        cutoff None or an objective value no point above which is of interest.  Returns dict of l, u (batch, n),
+        status (PROP_STATUS codes), changed and rounds (batch each)."""
+        n = self.n
+        l = np.ascontiguousarray(l, dtype=np.float64).reshape(-1, n)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, n)
+        B = l.shape[0]
+        assert u.shape[0] == B, 'l and u hold the same number of boxes'
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        cutoff = np.inf if cutoff is None else float(cutoff)
+        lo = np.zeros((B, n)); uo = np.zeros((B, n))
+        status = np.zeros(B, np.int32); changed = np.zeros(B, np.int32); rounds = np.zeros(B, np.int32)
+        rc = lib().mipx_propagate_batch(self._h, B, _ptr(l), _ptr(u), _ptr(ii), len(ii), cutoff, float(tol), int(max_rounds),
+                                        _ptr(lo), _ptr(uo), _ptr(status), _ptr(changed), _ptr(rounds))
+        self.ctx.check(rc, 'mipx_propagate_batch')
+        return dict(l=lo, u=uo, status=status, changed=changed, rounds=rounds)
+
     def solve_batch_dev(self, B, d_l, d_u, d_vstat, max_iter, d_status, d_obj, d_x, d_y, d_vout,
                         d_iters, d_npiv):
         rc = lib().mipx_lp_solve_batch_dev(self._h, int(B), d_l, d_u, d_vstat, int(max_iter),
@@ -1114,6 +1147,21 @@ class Tree:
         out = np.zeros(8, np.int64)
         self.problem.ctx.check(lib().mipx_tree_heuristic_stats(self._h, _ptr(out)), 'mipx_tree_heuristic_stats')
         return dict(zip(HEUR_STATS_KEYS, (int(v) for v in out)))
+
+    def set_propagation(self, max_rounds=True, use_cutoff=True):
+        """Propagate the bounds of every step's nodes over the rows on the GPU before their node LPs, in place on
+        their pool rows, the incumbent's objective as a cutoff row unless use_cutoff is False
+        (mipx_tree_set_propagation, include/mipx_prop.h; True: DEFAULT_PROPAGATION_ROUNDS rounds)."""
+        max_rounds = DEFAULT_PROPAGATION_ROUNDS if max_rounds is True else int(max_rounds)
+        self.problem.ctx.check(lib().mipx_tree_set_propagation(self._h, max_rounds, 1 if use_cutoff else 0),
+                               'mipx_tree_set_propagation')
+
+    def propagation_stats(self):
+        """dict(nodes, tightened, infeasible, bounds_changed, rounds, capped, reserved, kernel_us)
+        (mipx_tree_propagation_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_propagation_stats(self._h, _ptr(out)), 'mipx_tree_propagation_stats')
+        return dict(zip(PROP_STATS_KEYS, (int(v) for v in out)))
 
     def set_cut_migration(self, rows):
         """Reserve the top `rows` rows of the cut store for the cut rows of nodes received from other ranks, so

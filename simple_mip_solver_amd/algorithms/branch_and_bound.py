@@ -125,7 +125,7 @@ class BranchAndBound(BaseAlgorithm):
                  logging=False, max_run_time=INF, initial_primal_bound=INF, frontier_batch=None,
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
-                 **kwargs):
+                 propagate=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -194,7 +194,15 @@ class BranchAndBound(BaseAlgorithm):
         row, one GPU workgroup per point (include/mipx_heur.h); the best feasible point becomes the incumbent
         where it beats the one the search holds, before the step's nodes are pruned against it.  True takes 32
         points per step, an int that many; at most m + n moves per point.  The optimum is the same; the nodes
-        evaluated on the way differ.  Every step is then finished on the host.  Counters: `heuristic_stats`."""
+        evaluated on the way differ.  Every step is then finished on the host.  Counters: `heuristic_stats`.
+        propagate (extension; needs frontier_batch and gomory_cuts=False, not with comm, dual_function or
+        tree_record; default None = off): node presolve.  Before the node LPs of every step the engine tightens
+        the bounds of the step's nodes by activity-based bound propagation over the rows, the incumbent's
+        objective as one more row, one GPU workgroup per node (include/mipx_prop.h), in place: the children of a
+        node inherit what was tightened.  A node the propagation proves infeasible is closed as a node whose LP
+        was infeasible.  True takes at most 8 rounds per node, an int that many.  The optimum is the same; the
+        nodes evaluated on the way differ.  Every step is then finished on the host.  Counters:
+        `propagation_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -254,6 +262,20 @@ class BranchAndBound(BaseAlgorithm):
             'primal_heuristic needs gomory_cuts=False: the heuristic does not run on nodes with cut rows'
         self._primal_heuristic = primal_heuristic
         self.heuristic_stats = None
+        assert propagate is None or propagate is True or (
+            isinstance(propagate, int) and not isinstance(propagate, bool) and propagate > 0), \
+            'propagate is None, True or a positive number of rounds'
+        assert propagate is None or frontier_batch is not None, \
+            'propagate needs frontier_batch (it runs on the pool rows of the native engine)'
+        assert propagate is None or comm is None, 'propagate cannot be combined with comm'
+        assert propagate is None or kwargs.get('gomory_cuts', True) is False, \
+            'propagate needs gomory_cuts=False: the propagation does not see the cut rows of a node'
+        assert propagate is None or not dual_function, \
+            'propagate cannot be combined with dual_function: a propagated bound depends on the right-hand side'
+        assert propagate is None or not tree_record, \
+            'propagate cannot be combined with tree_record: bounds rebuilt from a lineage would miss the propagated ones'
+        self._propagate = propagate
+        self.propagation_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -430,6 +452,8 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_tree_record(True)
             if self._primal_heuristic:
                 self._native.set_heuristic(self._primal_heuristic)
+            if self._propagate:
+                self._native.set_propagation(self._propagate)
         st = None
         if self._comm is not None and not self._sharded:
             from simple_mip_solver_amd.parallel import shard_and_attach
@@ -489,6 +513,8 @@ class BranchAndBound(BaseAlgorithm):
             self.restart_stats = self._native.restart_stats()
         if self._primal_heuristic:
             self.heuristic_stats = self._native.heuristic_stats()
+        if self._propagate:
+            self.propagation_stats = self._native.propagation_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')

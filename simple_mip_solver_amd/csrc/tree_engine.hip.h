@@ -24,6 +24,7 @@
 #include "treerec_kernels.hip.h"
 #include "restart_kernels.hip.h"
 #include "heur_kernels.hip.h"
+#include "prop_kernels.hip.h"
 #include "cglp_kernels.hip.h"
 
 struct NodeRec {
@@ -306,6 +307,7 @@ struct StepBuf {
     hipEvent_t df_e0 = nullptr, df_e1 = nullptr;
     bool df_timed = false;
     int heur_n = 0;   // primal heuristic: the points of this step it was launched on (0: none)
+    int prop_n = 0;   // bound propagation: the nodes of this step it was launched on (0: none)
     int B = 0;
     bool in_flight = false;
     double inflight_min = std::numeric_limits<double>::infinity();   // lowest inherited bound of the batch (exchange record)
@@ -390,6 +392,19 @@ struct HeurState {
     hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
     int64_t tried = 0, feasible = 0, stuck = 0, capped = 0, repair = 0, lift = 0, installed = 0;
     double us = 0.0;                 // device time of heur_round_repair
+};
+
+// Bound propagation (include/mipx_prop.h): the option's parameters and, per step buffer, what comes down with
+// each step: [status | changed | rounds | capped] of cap int32 each.
+struct PropState {
+    bool on = false;
+    int max_rounds = 0, use_cutoff = 1;
+    int cap = 0;                     // nodes the step buffers are laid out for (the tree's max_batch)
+    double tol = 1e-6;
+    int32_t *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    int64_t nodes = 0, tightened = 0, infeasible = 0, changed = 0, rounds = 0, capped = 0;
+    double us = 0.0;                 // device time of prop_bounds
 };
 
 struct mipx_tree {
@@ -521,6 +536,7 @@ struct mipx_tree {
     TreeRec tr;
     RestartRec rs;
     HeurState hr;
+    PropState pg;
     // cut migration (mipx_tree_set_cut_migration): the top cm_rows rows of the cut store take the cut rows
     // of nodes received from other ranks, filled in order by the migration code (host-side fill level)
     int64_t cm_rows = 0, cm_used = 0;
@@ -728,6 +744,65 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         // dual bound of an emptied queue would end above the incumbent instead of on it)
         t->closed_min = std::fmin(t->closed_min, obj[best]);
         hr.installed++;
+    }
+    return MIPX_OK;
+}
+
+// ---- bound propagation (include/mipx_prop.h) ---------------------------------------------------------------
+// One launch of prop_bounds over `batch` boxes in device memory, queued on `st` (d_slot: the rows of d_l, d_u the
+// nodes are, or null for rows 0 .. batch - 1; d_l_out, d_u_out may be d_l, d_u).
+int prop_launch(const mipx_problem *p, hipStream_t st, int batch, const int32_t *d_slot, const double *d_l, const double *d_u,
+                const int32_t *d_int_idx, int n_int, double cutoff, double tol, int max_rounds, double *d_l_out,
+                double *d_u_out, int32_t *d_status, int32_t *d_changed, int32_t *d_rounds, int32_t *d_capped) {
+    mipx_ctx *ctx = p->ctx;
+    if (p->m > mipx::kPropMax || p->n > mipx::kPropMax) return fail(ctx, MIPX_ETOOBIG, "bound propagation: more than 1024 rows or columns");
+    if (batch <= 0) return MIPX_OK;
+    mipx::PropArgs a;
+    a.m = p->m; a.n = p->n; a.n_int = n_int; a.max_rounds = max_rounds;
+    a.cut = std::isfinite(cutoff) ? 1 : 0; a.tol = tol; a.cutoff = cutoff;
+    a.A = p->dA; a.b = p->db; a.c = p->dc; a.int_idx = d_int_idx; a.slot = d_slot;
+    a.l = d_l; a.u = d_u; a.l_out = d_l_out; a.u_out = d_u_out;
+    a.status_out = d_status; a.changed_out = d_changed; a.rounds_out = d_rounds; a.capped_out = d_capped;
+    hipLaunchKernelGGL(mipx::prop_bounds, dim3((unsigned)batch), dim3(mipx::kPropNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
+// The step's nodes through the propagation, in place on their pool rows, in front of their node LPs.
+int prop_step_launch(mipx_tree *t, StepBuf &S) {
+    PropState &pg = t->pg;
+    mipx_ctx *ctx = t->ctx;
+    hipStream_t st = ctx->stream;
+    const int bi = (int)(&S - t->buf), B = S.B;
+    int32_t *o = pg.d_out[bi];
+    const double cutoff = pg.use_cutoff ? t->primal : std::numeric_limits<double>::infinity();
+    HIP_TRY(ctx, hipEventRecord(pg.e0[bi], st));
+    const int rc = prop_launch(t->prob, st, B, S.d_slot, t->pool_l, t->pool_u, t->d_int_idx, t->n_int, cutoff, pg.tol,
+                               pg.max_rounds, t->pool_l, t->pool_u, o, o + pg.cap, o + 2 * pg.cap, o + 3 * pg.cap);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(pg.e1[bi], st));
+    S.prop_n = B;
+    return MIPX_OK;
+}
+
+// ... and what it found, once the step is done: the counters, and the nodes found infeasible (inf[k] != 0).
+int prop_step_collect(mipx_tree *t, StepBuf &S, std::vector<uint8_t> &inf) {
+    PropState &pg = t->pg;
+    const int bi = (int)(&S - t->buf), B = S.prop_n;
+    S.prop_n = 0;
+    int rc = tree_d2h(t, pg.h_out[bi], pg.d_out[bi], (size_t)pg.cap * 16);
+    if (rc) return rc;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, pg.e0[bi], pg.e1[bi]) == hipSuccess) pg.us += 1000.0 * ms;
+    const int32_t *status = pg.h_out[bi], *changed = status + pg.cap, *rounds = changed + pg.cap, *capped = rounds + pg.cap;
+    inf.assign((size_t)B, 0);
+    for (int k = 0; k < B; k++) {
+        pg.nodes++;
+        pg.changed += changed[k];
+        pg.rounds += rounds[k];
+        pg.capped += capped[k];
+        if (status[k] == MIPX_PROP_TIGHTENED) pg.tightened++;
+        if (status[k] == MIPX_PROP_INFEASIBLE) { pg.infeasible++; inf[(size_t)k] = 1; }
     }
     return MIPX_OK;
 }
@@ -1235,6 +1310,8 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
         HIP_TRY(ctx, hipEventRecord(S.done, st));
         return MIPX_OK;
     }
+    S.prop_n = 0;
+    if (t->pg.on && (rc = prop_step_launch(t, S))) return rc;   // (bound propagation: in place, in front of the node LPs)
     HIP_TRY(ctx, hipEventRecord(S.e0, st));
     // the root alone, never solved: one cold LP (above the register tiles it is spread over the chip, K1c)
     t->cold_launch = B == 1 && t->nodes.size() == 1 && S.recs[0].depth == 0 && S.recs[0].b_idx == -1 && !t->prob->anchor_on &&
@@ -1564,6 +1641,20 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
     int32_t *status = (int32_t *)(dval + DB), *bidx = status + OB, *mipf = bidx + OB, *nprobe = mipf + OB,
             *npiv = nprobe + OB, *dvar = npiv + OB, *ddir = dvar + DB;
     const int NB = (S.dive + 1) * B;  // output positions in use: the batch, then its dive children level by level
+    // bound propagation: a node it found infeasible is a node whose LP ended primal infeasible, whatever the LP on
+    // its unchanged row returned -- no probes, no children, and its plunge children are dropped
+    std::vector<uint8_t> prop_inf;
+    int64_t prop_asks = 0;   // probe requests of those nodes in the packed list
+    if (S.prop_n > 0) {
+        if ((rc = prop_step_collect(t, S, prop_inf))) return rc;
+        for (int k = 0; k < B; k++) {
+            if (!prop_inf[(size_t)k]) continue;
+            prop_asks += nprobe[k];
+            status[k] = 1;
+            nprobe[k] = 0;
+            if (S.dive > 0) dvar[k] = -1;
+        }
+    }
     // The node at position pos (level pos / B) was followed in place by a dive child at pos + B: it
     // counts when its LP was solved and it needs no strong-branching initialisation of its own (else
     // it is dropped and queued like any other child).  The decision taken after pos is dvar[pos].
@@ -1598,7 +1689,7 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
             // request); only a step with more than kAskCap of them -- the ramp-up -- reads the
             // per-node lists and solutions in bulk.
             const int32_t asked = *(const int32_t *)(S.h_pack + S.ask_off);
-            if (asked == total && asked <= kAskCap) {
+            if (asked == total + prop_asks && asked <= kAskCap) {
                 using Ask = mipx::ScoreArgs::Ask;
                 const Ask *ask = (const Ask *)(S.h_pack + S.ask_off + 16);
                 std::vector<Ask> es(ask, ask + asked);
@@ -1606,6 +1697,7 @@ int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
                     return a.node < b.node || (a.node == b.node && a.k < b.k);
                 });
                 for (const Ask &e : es) {
+                    if (!prop_inf.empty() && prop_inf[(size_t)e.node]) continue;
                     pair_pos.push_back(e.node);
                     pair_slot.push_back(slots[e.node]);
                     pair_var.push_back(t->int_idx[e.k]);
@@ -2864,6 +2956,15 @@ void mipx_tree_destroy(mipx_tree *t) {
             if (hr.e1[k]) (void)hipEventDestroy(hr.e1[k]);
         }
     }
+    {
+        PropState &pg = t->pg;
+        for (int k = 0; k < 3; k++) {
+            if (pg.d_out[k]) (void)hipFree(pg.d_out[k]);
+            if (pg.h_out[k]) (void)hipHostFree(pg.h_out[k]);
+            if (pg.e0[k]) (void)hipEventDestroy(pg.e0[k]);
+            if (pg.e1[k]) (void)hipEventDestroy(pg.e1[k]);
+        }
+    }
     if (t->h_pairs) (void)hipHostFree(t->h_pairs);
     if (t->h_pres) (void)hipHostFree(t->h_pres);
     if (t->h_tab) (void)hipHostFree(t->h_tab);
@@ -3299,6 +3400,7 @@ int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps) {
     if (c && t->df.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the dual function (mipx_tree_set_dual_record)");
     if (c && t->tr.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the tree record (mipx_tree_set_tree_record)");
     if (c && t->hr.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the primal heuristic (mipx_tree_set_heuristic)");
+    if (c && t->pg.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the bound propagation (mipx_tree_set_propagation)");
     t->comm = c;
     t->x_every = c ? every_steps : 0;
     if (!c) return MIPX_OK;
@@ -3679,3 +3781,4 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "cglp_api.hip.h"
 #include "restart_api.hip.h"
 #include "heur_api.hip.h"
+#include "prop_api.hip.h"
