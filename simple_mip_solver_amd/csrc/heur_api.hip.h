@@ -63,13 +63,14 @@ int mipx_tree_set_heuristic(mipx_tree *t, int points_per_step, int every_steps, 
             if (hr.d_out[k]) (void)hipFree(hr.d_out[k]);
             if (hr.h_out[k]) (void)hipHostFree(hr.h_out[k]);
             hr.d_x[k] = nullptr; hr.d_out[k] = nullptr; hr.h_out[k] = nullptr;
-            int rc = dmalloc(ctx, &hr.d_x[k], (size_t)P * n) | dmalloc(ctx, &hr.d_out[k], (size_t)P * 20);
+            const size_t out_bytes = step_layout::HeurOut((size_t)P).bytes();
+            int rc = dmalloc(ctx, &hr.d_x[k], (size_t)P * n) | dmalloc(ctx, &hr.d_out[k], out_bytes);
             if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&hr.h_out[k], (size_t)P * 20));
+            HIP_TRY(ctx, hipHostMalloc((void **)&hr.h_out[k], out_bytes));
             if (!hr.e0[k]) HIP_TRY(ctx, hipEventCreate(&hr.e0[k]));
             if (!hr.e1[k]) HIP_TRY(ctx, hipEventCreate(&hr.e1[k]));
         }
-        hr.cap = P;   // (the layout of the step buffers: [obj | status | moves] of hr.cap each)
+        hr.cap = P;   // (the step buffers are laid out for hr.cap points: step_layout::HeurOut)
     }
     hr.points = P;
     hr.every = every_steps;

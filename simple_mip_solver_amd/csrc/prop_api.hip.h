@@ -54,15 +54,15 @@ int mipx_tree_set_propagation(mipx_tree *t, int max_rounds, int use_cutoff) {
     PropState &pg = t->pg;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (pg.cap == 0) {
-        const size_t cap = (size_t)t->max_batch;
+        const size_t out_bytes = step_layout::PropOut((size_t)t->max_batch).bytes();
         for (int k = 0; k < 3; k++) {
-            int rc = dmalloc(ctx, &pg.d_out[k], 4 * cap);
+            int rc = dmalloc(ctx, &pg.d_out[k], out_bytes / 4);
             if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&pg.h_out[k], 4 * cap * 4));
+            HIP_TRY(ctx, hipHostMalloc((void **)&pg.h_out[k], out_bytes));
             HIP_TRY(ctx, hipEventCreate(&pg.e0[k]));
             HIP_TRY(ctx, hipEventCreate(&pg.e1[k]));
         }
-        pg.cap = t->max_batch;   // (the layout of the step buffers: [status | changed | rounds | capped] of pg.cap each)
+        pg.cap = t->max_batch;   // (the step buffers are laid out for pg.cap nodes: step_layout::PropOut)
     }
     pg.max_rounds = max_rounds;
     pg.use_cutoff = use_cutoff ? 1 : 0;

@@ -26,6 +26,7 @@
 #include "heur_kernels.hip.h"
 #include "prop_kernels.hip.h"
 #include "cglp_kernels.hip.h"
+#include "step_layout.h"
 
 struct NodeRec {
     double key;          // queue key: dual bound (best first) or -depth (depth first)
@@ -247,20 +248,14 @@ struct BucketQueue {
 // Per-step device outputs and host staging, double-buffered so that the host bookkeeping of step
 // k overlaps the node-LP kernel of step k+1 (frontier batches > 1).
 struct StepBuf {
-    int32_t *d_slot = nullptr, *d_status = nullptr, *d_iters = nullptr, *d_npiv = nullptr,
-            *d_bidx = nullptr, *d_mipf = nullptr, *d_nprobe = nullptr, *d_plist = nullptr;
-    int32_t *d_ask_count = nullptr;          // [count | pad] then kAskCap entries, inside d_pack
-    mipx::ScoreArgs::Ask *d_ask = nullptr;
-    size_t ask_off = 0;
-    double *d_obj = nullptr, *d_x = nullptr, *d_bval = nullptr, *d_dval = nullptr;
-    int32_t *d_dvar = nullptr, *d_ddir = nullptr;   // in-place dives of the step (per parent)
+    int32_t *d_slot = nullptr, *d_iters = nullptr, *d_plist = nullptr;
+    double *d_x = nullptr;
     int8_t *d_vout = nullptr;
-    // what the host reads back every step, packed so that ONE copy into pinned memory fetches it:
-    // [obj | bval] (2 * max_batch f64 each: the batch, then its dive children) [dive_val]
-    // (max_batch f64), then [status | bidx | mipf | nprobe | npiv] (2 * max_batch i32 each)
-    // [dive_var | dive_dir] (max_batch i32 each), then the probe requests
+    // what the host reads back every step, packed so that ONE copy into pinned memory fetches it: the layout in
+    // use (for the tree's dive depth) and its device view, both set by layout_pack
     char *d_pack = nullptr, *h_pack = nullptr;
-    size_t pack_bytes = 0;
+    step_layout::StepPack pack{1, 0, 0, 0};
+    step_layout::StepPack::View<char> d{};
     int32_t *h_slot = nullptr;  // pinned staging of the batch's pool rows
     hipEvent_t e0 = nullptr, e1 = nullptr, done = nullptr;
     hipEvent_t k2a = nullptr, k2b = nullptr, k3b = nullptr;   // cut rounds: around K2 and K3 of a round
@@ -280,14 +275,14 @@ struct StepBuf {
             *cs_need_tab = nullptr;
     double *d_y = nullptr, *cs_before = nullptr, *slab_pi = nullptr, *slab_pi0 = nullptr,
            *dump_T = nullptr, *dump_vec = nullptr;
-    int32_t *h_cs = nullptr;   // pinned: [counters (4) | state fields 0..6 + w_ncut (8 x max_batch)]
+    int32_t *h_cs = nullptr;   // pinned: step_layout::CutState
     int dive = 0;  // this step was launched with the in-place dive: children in a row per node
     bool scored_once = false;  // K4 ran on this step (the first run's request counter was zeroed by K1)
     // the step finished on the device (finish_kernels.hip.h): the parents' records and the pool rows the
     // children may take go up with the batch, a summary + compact lists come back
     bool fast = false;
     int tabv = 0;                                // the table version this step's finish writes
-    char *d_par = nullptr, *h_par = nullptr;     // [par_d (2 MB f64) | par_i (4 MB i32) | budget (per MB i32)]
+    char *d_par = nullptr, *h_par = nullptr;     // step_layout::ParentBlock
     int32_t *c_info = nullptr, *c_cnt = nullptr, *c_eval = nullptr, *c_flag = nullptr;
     double *c_val = nullptr;
     mipx::FinishSummary *d_sum = nullptr;
@@ -295,7 +290,7 @@ struct StepBuf {
     int32_t *d_dead = nullptr;
     mipx::PcSample *d_samples = nullptr, *h_samples = nullptr;   // h_samples: pinned staging of a host-finished step's samples
     int32_t *d_skeys = nullptr;                  // the samples' table entries, densely (pc_apply scans them)
-    char *h_fin = nullptr;                       // pinned: [summary | table block | open entries | dead rows]
+    char *h_fin = nullptr;                       // pinned: step_layout::FinishBlock
     std::vector<int32_t> budget;
     // host spill: the batch's spilled nodes, staged pinned as [offsets (rl_n + 1) | rows | records] and unpacked
     // into their new rows on the launch stream before the node LPs read them
@@ -380,7 +375,7 @@ struct RestartRec {
 };
 
 // Primal heuristic (include/mipx_heur.h): the option's parameters, the root's bounds on the device, and per step
-// buffer the rounded points and what comes down with each step: [obj (P f64) | status (P i32) | moves (2 P i32)].
+// buffer the rounded points and what comes down with each step (step_layout::HeurOut).
 struct HeurState {
     bool on = false;
     int points = 0, every = 1, max_moves = 0;
@@ -395,7 +390,7 @@ struct HeurState {
 };
 
 // Bound propagation (include/mipx_prop.h): the option's parameters and, per step buffer, what comes down with
-// each step: [status | changed | rounds | capped] of cap int32 each.
+// each step (step_layout::PropOut).
 struct PropState {
     bool on = false;
     int max_rounds = 0, use_cutoff = 1;
@@ -638,9 +633,9 @@ int launch_lp(mipx_tree *t, int batch, const double *l, const double *u, const i
         const TabPtr tb = tab_at(t, t->fast_ok ? t->tab_host : 0);
         a.int_idx = t->d_int_idx; a.cost_l = tb.cl; a.cost_r = tb.cr; a.has_entry = tb.has;
         a.dive_cutoff = t->primal;
-        a.dive_var = dive->d_dvar; a.dive_dir = dive->d_ddir; a.dive_val = dive->d_dval;
+        a.dive_var = dive->d.dvar; a.dive_dir = dive->d.ddir; a.dive_val = dive->d.dval;
         a.dive_preset = 1;           // the kernel itself marks "no child / no dive" first
-        a.zero16 = dive->d_ask_count; // and zeroes K4's request counter
+        a.zero16 = dive->d.ask_count; // and zeroes K4's request counter
     }
     a.l = l; a.u = u; a.vstat_in = v; a.slot = slot; a.max_iter = max_iter;
     a.cold = t->cold_launch ? 1 : 0;   // (the root's step: its pool row holds no basis)
@@ -701,11 +696,10 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
     mipx_ctx *ctx = t->ctx;
     hipStream_t st = ctx->stream;
     const int bi = (int)(&S - t->buf), P = std::min(S.B, hr.points);
-    double *obj = (double *)hr.d_out[bi];
-    int32_t *status = (int32_t *)(obj + hr.cap), *moves = status + hr.cap;
+    const auto o = step_layout::HeurOut((size_t)hr.cap).view(hr.d_out[bi]);
     HIP_TRY(ctx, hipEventRecord(hr.e0[bi], st));
     const int rc = heur_launch(t->prob, st, P, S.d_x, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
-                               nullptr, S.d_status, hr.d_x[bi], obj, status, moves);
+                               nullptr, S.d.status, hr.d_x[bi], o.obj, o.status, o.moves);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(hr.e1[bi], st));
     S.heur_n = P;
@@ -718,12 +712,13 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
     HeurState &hr = t->hr;
     const int bi = (int)(&S - t->buf), P = S.heur_n, n = t->n;
     S.heur_n = 0;
-    int rc = tree_d2h(t, hr.h_out[bi], hr.d_out[bi], (size_t)hr.cap * 20);
+    const step_layout::HeurOut lay((size_t)hr.cap);
+    int rc = tree_d2h(t, hr.h_out[bi], hr.d_out[bi], lay.bytes());
     if (rc) return rc;
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, hr.e0[bi], hr.e1[bi]) == hipSuccess) hr.us += 1000.0 * ms;
-    const double *obj = (const double *)hr.h_out[bi];
-    const int32_t *status = (const int32_t *)(obj + hr.cap), *moves = status + hr.cap;
+    const auto o = lay.view((const char *)hr.h_out[bi]);
+    const double *obj = o.obj; const int32_t *status = o.status, *moves = o.moves;
     int best = -1;
     for (int k = 0; k < P; k++) {
         if (status[k] == MIPX_HEUR_SKIPPED) continue;
@@ -774,11 +769,11 @@ int prop_step_launch(mipx_tree *t, StepBuf &S) {
     mipx_ctx *ctx = t->ctx;
     hipStream_t st = ctx->stream;
     const int bi = (int)(&S - t->buf), B = S.B;
-    int32_t *o = pg.d_out[bi];
+    const auto o = step_layout::PropOut((size_t)pg.cap).view(pg.d_out[bi]);
     const double cutoff = pg.use_cutoff ? t->primal : std::numeric_limits<double>::infinity();
     HIP_TRY(ctx, hipEventRecord(pg.e0[bi], st));
     const int rc = prop_launch(t->prob, st, B, S.d_slot, t->pool_l, t->pool_u, t->d_int_idx, t->n_int, cutoff, pg.tol,
-                               pg.max_rounds, t->pool_l, t->pool_u, o, o + pg.cap, o + 2 * pg.cap, o + 3 * pg.cap);
+                               pg.max_rounds, t->pool_l, t->pool_u, o.status, o.changed, o.rounds, o.capped);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(pg.e1[bi], st));
     S.prop_n = B;
@@ -790,19 +785,20 @@ int prop_step_collect(mipx_tree *t, StepBuf &S, std::vector<uint8_t> &inf) {
     PropState &pg = t->pg;
     const int bi = (int)(&S - t->buf), B = S.prop_n;
     S.prop_n = 0;
-    int rc = tree_d2h(t, pg.h_out[bi], pg.d_out[bi], (size_t)pg.cap * 16);
+    const step_layout::PropOut lay((size_t)pg.cap);
+    int rc = tree_d2h(t, pg.h_out[bi], pg.d_out[bi], lay.bytes());
     if (rc) return rc;
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, pg.e0[bi], pg.e1[bi]) == hipSuccess) pg.us += 1000.0 * ms;
-    const int32_t *status = pg.h_out[bi], *changed = status + pg.cap, *rounds = changed + pg.cap, *capped = rounds + pg.cap;
+    const auto o = lay.view((const int32_t *)pg.h_out[bi]);
     inf.assign((size_t)B, 0);
     for (int k = 0; k < B; k++) {
         pg.nodes++;
-        pg.changed += changed[k];
-        pg.rounds += rounds[k];
-        pg.capped += capped[k];
-        if (status[k] == MIPX_PROP_TIGHTENED) pg.tightened++;
-        if (status[k] == MIPX_PROP_INFEASIBLE) { pg.infeasible++; inf[(size_t)k] = 1; }
+        pg.changed += o.changed[k];
+        pg.rounds += o.rounds[k];
+        pg.capped += o.capped[k];
+        if (o.status[k] == MIPX_PROP_TIGHTENED) pg.tightened++;
+        if (o.status[k] == MIPX_PROP_INFEASIBLE) { pg.infeasible++; inf[(size_t)k] = 1; }
     }
     return MIPX_OK;
 }
@@ -810,21 +806,19 @@ int prop_step_collect(mipx_tree *t, StepBuf &S, std::vector<uint8_t> &inf) {
 constexpr int kAskCap = 2048;  // probe requests per step carried in the packed read-back
 constexpr int kMaxDive = 8;    // dive children in a row per node (buffers are sized for it)
 
-// What the host reads back every step, packed so that ONE copy into pinned memory fetches it, laid
-// out for L = 1 + dive output levels of max_batch positions each:
-//   [obj | bval] (L * MB f64 each) [dive_val] ((L - 1 or 1) * MB f64)
-//   [status | bidx | mipf | nprobe | npiv] (L * MB i32 each) [dive_var | dive_dir] ((L - 1 or 1) * MB each)
-//   then the probe requests
+// The step buffers (step_layout.h) at this tree's dimensions.  The element sizes the layouts take are the
+// kernels' types: a probe request, an open entry, and the summary in front of the table block at 128.
+using step_layout::CutState;
+using Ask = mipx::ScoreArgs::Ask;
+static_assert(sizeof(mipx::FinishSummary) == 128, "step_layout::FinishBlock keeps 128 bytes for the summary");
+static_assert(alignof(Ask) <= 16 && alignof(mipx::OpenEntry) <= 32, "step_layout aligns requests to 16, open entries to 32");
+step_layout::StepPack step_pack(const mipx_tree *t, int levels) { return {(size_t)levels, (size_t)t->max_batch, (size_t)kAskCap, sizeof(Ask)}; }
+step_layout::FinishBlock finish_block(const mipx_tree *t, size_t per) { return {t->tab_bytes, per, (size_t)t->max_batch, sizeof(mipx::OpenEntry)}; }
+
+// The packed read-back laid out for `levels` = 1 + dive output levels: the layout and its device view.
 void layout_pack(mipx_tree *t, StepBuf &S, int levels) {
-    const size_t MB = (size_t)t->max_batch, OB = (size_t)levels * MB, DB = (size_t)(levels > 1 ? levels - 1 : 1) * MB;
-    S.d_obj = (double *)S.d_pack; S.d_bval = S.d_obj + OB; S.d_dval = S.d_bval + OB;
-    S.d_status = (int32_t *)(S.d_dval + DB); S.d_bidx = S.d_status + OB; S.d_mipf = S.d_bidx + OB;
-    S.d_nprobe = S.d_mipf + OB; S.d_npiv = S.d_nprobe + OB;
-    S.d_dvar = S.d_npiv + OB; S.d_ddir = S.d_dvar + DB;
-    S.ask_off = (OB * (2 * 8 + 5 * 4) + DB * (8 + 2 * 4) + 15) / 16 * 16;
-    S.pack_bytes = S.ask_off + 16 + (size_t)kAskCap * sizeof(mipx::ScoreArgs::Ask);
-    S.d_ask_count = (int32_t *)((char *)S.d_pack + S.ask_off);
-    S.d_ask = (mipx::ScoreArgs::Ask *)((char *)S.d_pack + S.ask_off + 16);
+    S.pack = step_pack(t, levels);
+    S.d = S.pack.view(S.d_pack);
 }
 
 int launch_score(mipx_tree *t, StepBuf &S, int batch, bool side = false, bool no_ask = false, int side_stream = -1) {
@@ -832,17 +826,17 @@ int launch_score(mipx_tree *t, StepBuf &S, int batch, bool side = false, bool no
     hipStream_t where = side_stream == 2 ? t->stf : on_st2 ? t->st2 : t->ctx->stream;   // (2: the finish stream)
     mipx::ScoreArgs s;
     s.n = t->n; s.n_int = t->n_int; s.batch = batch; s.rule = t->rule;
-    s.int_idx = t->d_int_idx; s.x = S.d_x; s.status = S.d_status;
+    s.int_idx = t->d_int_idx; s.x = S.d_x; s.status = S.d.status;
     const TabPtr tb = tab_at(t, t->fast_ok ? t->tab_host : 0);
     s.cost_l = side ? t->d_cost_l2 : tb.cl; s.cost_r = side ? t->d_cost_r2 : tb.cr;
     s.has_entry = side ? t->d_has2 : tb.has;
-    s.branch_idx = S.d_bidx; s.branch_val = S.d_bval; s.mip_feasible = S.d_mipf;
-    s.n_probe = S.d_nprobe;
+    s.branch_idx = S.d.bidx; s.branch_val = S.d.bval; s.mip_feasible = S.d.mipf;
+    s.n_probe = S.d.nprobe;
     s.probe_list = S.d_plist;
-    s.ask_count = S.d_ask_count; s.ask_cap = kAskCap; s.ask = (side || no_ask) ? nullptr : S.d_ask;
+    s.ask_count = S.d.ask_count; s.ask_cap = kAskCap; s.ask = (side || no_ask) ? nullptr : (Ask *)S.d.ask;
     s.ask_nodes = S.B;  // dive children (positions >= B) are never probed in their own step
     if (!side && !no_ask && !(S.dive && batch == (S.dive + 1) * S.B && !S.scored_once))
-        HIP_TRY(t->ctx, hipMemsetAsync(S.d_ask_count, 0, 16, side_stream == 2 ? t->stf : t->ctx->stream));
+        HIP_TRY(t->ctx, hipMemsetAsync(S.d.ask_count, 0, 16, side_stream == 2 ? t->stf : t->ctx->stream));
     if (!no_ask) S.scored_once = true;
     hipLaunchKernelGGL(mipx::branch_score, dim3(batch), dim3(64), 0, where, s);
     HIP_TRY(t->ctx, hipGetLastError());
@@ -885,21 +879,19 @@ int launch_finish(mipx_tree *t, StepBuf &S) {
     t->tab_late[S.tabv] = false;   // (written afresh: a copy of the tail, which holds every late update queued so far)
     if (t->rule == 1)
         HIP_TRY(ctx, hipMemcpyAsync(tab_at(t, S.tabv).cl, tab_at(t, prev).cl, t->tab_bytes, hipMemcpyDeviceToDevice, st));
-    const int B = S.B, L = t->dive + 1;
+    const int B = S.B;
     const size_t MB = (size_t)t->max_batch;
+    const auto par = step_layout::ParentBlock((size_t)B, 2 * (1 + (size_t)t->dive)).view((const char *)S.d_par);
     mipx::FinishArgs g;
     g.n = t->n; g.m = t->m; g.B = B; g.dive = S.dive; g.rule = t->rule;
-    g.status = S.d_status; g.bidx = S.d_bidx; g.mipf = S.d_mipf; g.nprobe = S.d_nprobe; g.npiv = S.d_npiv;
-    g.dvar = S.d_dvar; g.ddir = S.d_ddir; g.obj = S.d_obj; g.bval = S.d_bval; g.dval = S.d_dval;
-    g.ask_count = S.d_ask_count; g.ask_cap = kAskCap; g.vout = S.d_vout;
+    g.status = S.d.status; g.bidx = S.d.bidx; g.mipf = S.d.mipf; g.nprobe = S.d.nprobe; g.npiv = S.d.npiv;
+    g.dvar = S.d.dvar; g.ddir = S.d.ddir; g.obj = S.d.obj; g.bval = S.d.bval; g.dval = S.d.dval;
+    g.ask_count = S.d.ask_count; g.ask_cap = kAskCap; g.vout = S.d_vout;
     g.slot = S.d_slot;
-    g.par_d = (const double *)S.d_par;
-    g.par_i = (const int32_t *)(S.d_par + 2 * (size_t)B * 8);
-    g.budget = g.par_i + 4 * (size_t)B;
+    g.par_d = par.par_d; g.par_i = par.par_i; g.budget = par.budget;
     g.pool_l = t->pool_l; g.pool_u = t->pool_u; g.pool_v = t->pool_v; g.primal = t->d_primal;
     g.c_info = S.c_info; g.c_cnt = S.c_cnt; g.c_eval = S.c_eval; g.c_val = S.c_val; g.c_flag = S.c_flag;
     g.sum = S.d_sum; g.open = S.d_open; g.dead = S.d_dead; g.samples = S.d_samples; g.sample_keys = S.d_skeys;
-    (void)L;
     g.c_run = S.c_val + 2 * MB;
     hipLaunchKernelGGL(mipx::finish_candidates, dim3((B + 255) / 256), dim3(256), 0, st, g);
     hipLaunchKernelGGL(mipx::finish_prefix_min, dim3(1), dim3(1024), 0, st, g);
@@ -1257,15 +1249,15 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
             return fail(ctx, MIPX_ENOMEM, "tree: fewer free pool rows than the batch's children budget");
         S.budget.assign(t->free_slots.end() - (std::ptrdiff_t)need, t->free_slots.end());
         t->free_slots.resize(t->free_slots.size() - need);
-        double *pd = (double *)S.h_par;
-        int32_t *pi = (int32_t *)(S.h_par + 2 * (size_t)B * 8);
+        const step_layout::ParentBlock lay((size_t)B, per);
+        const auto par = lay.view(S.h_par);
         for (int k = 0; k < B; k++) {
             const NodeRec &nd = S.recs[(size_t)k];
-            pd[k] = nd.dual_bound; pd[B + k] = nd.b_val;
-            pi[k] = nd.b_idx; pi[B + k] = nd.b_dir; pi[2 * B + k] = nd.depth; pi[3 * B + k] = nd.anchor;
+            par.par_d[k] = nd.dual_bound; par.par_d[B + k] = nd.b_val;
+            par.par_i[k] = nd.b_idx; par.par_i[B + k] = nd.b_dir; par.par_i[2 * B + k] = nd.depth; par.par_i[3 * B + k] = nd.anchor;
         }
-        std::memcpy(pi + 4 * (size_t)B, S.budget.data(), need * 4);
-        HIP_TRY(ctx, hipMemcpyAsync(S.d_par, S.h_par, 2 * (size_t)B * 8 + (4 * (size_t)B + need) * 4, hipMemcpyHostToDevice, st));
+        std::memcpy(par.budget, S.budget.data(), need * 4);
+        HIP_TRY(ctx, hipMemcpyAsync(S.d_par, S.h_par, lay.bytes(), hipMemcpyHostToDevice, st));
     }
     std::memcpy(S.h_slot, slots.data(), (size_t)B * 4);
     for (int k = 0; k < B; k++) S.h_slot[B + k] = S.recs[(size_t)k].anchor;  // [pool rows | anchor-table entries]
@@ -1302,8 +1294,8 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
         HIP_TRY(ctx, hipEventRecord(S.e0, st));
         t->cold_launch = B == 1 && t->nodes.size() == 1 && S.recs[0].depth == 0 && S.recs[0].b_idx == -1 && S.recs[0].ncut == 0 &&
                          !t->prob->anchor_on && !t->rs.on;   // (the root alone, never solved, no cut yet: one cold LP)
-        rc = launch_lp(t, B, t->pool_l, t->pool_u, t->pool_v, S.d_slot, 0, S.d_status, S.d_obj, S.d_x,
-                       S.d_vout, S.d_iters, S.d_npiv, nullptr, nullptr, S.d_slot + B, &cl);
+        rc = launch_lp(t, B, t->pool_l, t->pool_u, t->pool_v, S.d_slot, 0, S.d.status, S.d.obj, S.d_x,
+                       S.d_vout, S.d_iters, S.d.npiv, nullptr, nullptr, S.d_slot + B, &cl);
         if (rc) return rc;
         HIP_TRY(ctx, hipEventRecord(S.e1, st));
         if ((rc = launch_score(t, S, B, false, true))) return rc;
@@ -1316,8 +1308,8 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
     // the root alone, never solved: one cold LP (above the register tiles it is spread over the chip, K1c)
     t->cold_launch = B == 1 && t->nodes.size() == 1 && S.recs[0].depth == 0 && S.recs[0].b_idx == -1 && !t->prob->anchor_on &&
                      !t->rs.on;   // (a restart's root is a seed: its row holds the source's root basis)
-    rc = launch_lp(t, B, t->pool_l, t->pool_u, t->pool_v, S.d_slot, 0, S.d_status, S.d_obj,
-                   S.d_x, S.d_vout, S.d_iters, S.d_npiv, nullptr, S.dive ? &S : nullptr, S.d_slot + B, nullptr,
+    rc = launch_lp(t, B, t->pool_l, t->pool_u, t->pool_v, S.d_slot, 0, S.d.status, S.d.obj,
+                   S.d_x, S.d_vout, S.d_iters, S.d.npiv, nullptr, S.dive ? &S : nullptr, S.d_slot + B, nullptr,
                    t->df.on ? S.df_y : nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(S.e1, st));
@@ -1349,7 +1341,8 @@ int tree_cut_rounds(mipx_tree *t, StepBuf &S) {
     mipx_ctx *ctx = t->ctx;
     hipStream_t st = ctx->stream;
     const int B = S.B, n = t->n;
-    const size_t MB = (size_t)t->max_batch;
+    const CutState cs((size_t)t->max_batch);
+    const int32_t *cnt = cs.counters(S.h_cs);
     int maxc = 0;
     for (int k = 0; k < B; k++) maxc = std::max(maxc, (int)S.recs[(size_t)k].ncut);
     // Without exact_tableau every LP launch of the loop dumps the tableau it ends with, and K2 reads that:
@@ -1363,7 +1356,7 @@ int tree_cut_rounds(mipx_tree *t, StepBuf &S) {
         ra.n = n; ra.m0 = t->m; ra.mstride = t->mrows; ra.kc = t->kc; ra.batch = B; ra.round = round;
         ra.max_rounds = t->cp.max_cut_generation_iterations;
         ra.progress_tol = t->cp.cutting_plane_progress_tolerance; ra.max_dual_bound = t->cp.max_dual_bound;
-        ra.status = S.d_status; ra.obj = S.d_obj; ra.mipf = S.d_mipf; ra.y = S.d_y; ra.vstat = S.d_vout;
+        ra.status = S.d.status; ra.obj = S.d.obj; ra.mipf = S.d.mipf; ra.y = S.d_y; ra.vstat = S.d_vout;
         ra.ncut = S.w_ncut; ra.ids = S.w_ids; ra.state = S.cs_state; ra.obj_before = S.cs_before;
         ra.active = S.cs_active; ra.resolve = S.cs_resolve; ra.counters = S.cs_counters;
         ra.have_dump = fused ? 1 : 0; ra.need_tab = S.cs_need_tab;
@@ -1371,12 +1364,12 @@ int tree_cut_rounds(mipx_tree *t, StepBuf &S) {
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(S.h_cs, S.cs_counters, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (S.h_cs[0] == 0) break;   // nobody generates any more
+        if (cnt[CutState::kActive] == 0) break;   // nobody generates any more
         // the tableau of every generating node's basis (refactorisation from the slack basis -- or,
         // without exact_tableau, from the root's anchor where the node has no cut rows -- then zero
         // iterations: the basis is optimal), dumped for K2
         int rc = MIPX_OK;
-        if (S.h_cs[3] > 0) {
+        if (cnt[CutState::kNeedTab] > 0) {
             CutLaunch cl;
             cl.ncut = S.w_ncut; cl.ids = S.w_ids; cl.vstat_by_node = 1; cl.active = S.cs_need_tab;
             cl.m_rows = t->m + maxc; cl.dT = S.dump_T; cl.dvec = S.dump_vec; cl.didx = S.dump_idx;
@@ -1440,16 +1433,16 @@ int tree_cut_rounds(mipx_tree *t, StepBuf &S) {
             if (hipEventElapsedTime(&a, S.k2a, S.k2b) == hipSuccess) t->k2_ms += a;
             if (hipEventElapsedTime(&b, S.k2b, S.k3b) == hipSuccess) t->k3_ms += b;   // (pool_append + K3)
         }
-        const int changed = S.h_cs[1];
-        maxc = std::max(maxc, (int)S.h_cs[2]);
+        const int changed = cnt[CutState::kChanged];
+        maxc = std::max(maxc, (int)cnt[CutState::kMaxNcut]);
         if (changed > 0) {   // re-solve where rows came or went, warm from the node's own basis (:319)
             CutLaunch rl;
             rl.ncut = S.w_ncut; rl.ids = S.w_ids; rl.vstat_by_node = 1; rl.active = S.cs_resolve;
             rl.y = S.d_y; rl.m_rows = t->m + maxc;
             if (fused) { rl.dT = S.dump_T; rl.dvec = S.dump_vec; rl.didx = S.dump_idx; }
             rl.no_anchor = true;   // (a node that changed rows has, or just had, cut rows)
-            rc = launch_lp(t, B, t->pool_l, t->pool_u, S.d_vout, S.d_slot, 0, S.d_status, S.d_obj, S.d_x,
-                           S.d_vout, S.d_iters, S.d_npiv, nullptr, nullptr, nullptr, &rl);
+            rc = launch_lp(t, B, t->pool_l, t->pool_u, S.d_vout, S.d_slot, 0, S.d.status, S.d.obj, S.d_x,
+                           S.d_vout, S.d_iters, S.d.npiv, nullptr, nullptr, nullptr, &rl);
             if (rc) return rc;
             if ((rc = launch_score(t, S, B, false, true))) return rc;
             t->lps += changed;
@@ -1458,15 +1451,15 @@ int tree_cut_rounds(mipx_tree *t, StepBuf &S) {
     }
     // per node: rounds and the six GMIC counters, its final number of cut rows
     // (fields 0..6 lie behind one another on the device; with a full batch also on the host: one copy)
-    if ((size_t)B == MB) {
-        HIP_TRY(ctx, hipMemcpyAsync(S.h_cs + 4, S.cs_state, 7 * (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    static_assert((int)CutState::kStateFields == (int)mipx::CF_N_REMOVED + 1, "the state fields the host reads: rounds .. n_removed");
+    if ((size_t)B == cs.max_batch) {
+        HIP_TRY(ctx, hipMemcpyAsync(cs.field(S.h_cs, 0), S.cs_state, CutState::kStateFields * (size_t)B * 4, hipMemcpyDeviceToHost, st));
     } else {
-        for (int f = 0; f < 7; f++)
-            HIP_TRY(ctx, hipMemcpyAsync(S.h_cs + 4 + (size_t)f * MB, S.cs_state + (size_t)f * B, (size_t)B * 4,
-                                        hipMemcpyDeviceToHost, st));
+        for (int f = 0; f < CutState::kStateFields; f++)
+            HIP_TRY(ctx, hipMemcpyAsync(cs.field(S.h_cs, f), S.cs_state + (size_t)f * B, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(ctx, hipMemcpyAsync(S.h_cs + 4 + 7 * MB, S.w_ncut, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(S.h_cs + 4 + 8 * MB, S.cs_state + (size_t)mipx::CF_DROPPED * B, (size_t)B * 4,
+    HIP_TRY(ctx, hipMemcpyAsync(cs.field(S.h_cs, CutState::kRowsAfter), S.w_ncut, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(cs.field(S.h_cs, CutState::kDropped), S.cs_state + (size_t)mipx::CF_DROPPED * B, (size_t)B * 4,
                                 hipMemcpyDeviceToHost, st));
     // the final scoring of the batch (branching variable, strong-branching requests)
     int rc = launch_score(t, S, B);
@@ -1474,8 +1467,8 @@ int tree_cut_rounds(mipx_tree *t, StepBuf &S) {
     HIP_TRY(ctx, hipEventRecord(S.done, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     for (int k = 0; k < B; k++) {
-        for (int f = 0; f < 7; f++) t->cut_totals[f] += S.h_cs[4 + (size_t)f * MB + k];
-        t->cut_totals[7] += S.h_cs[4 + 8 * MB + k];
+        for (int f = 0; f < CutState::kStateFields; f++) t->cut_totals[f] += *cs.field(S.h_cs, f, (size_t)k);
+        t->cut_totals[7] += *cs.field(S.h_cs, CutState::kDropped, (size_t)k);
     }
     return MIPX_OK;
 }
@@ -1510,30 +1503,30 @@ int tree_finish_fast(mipx_tree *t, StepBuf &S, const mipx::FinishSummary &sum, s
     if (sum.n_open < 0 || (size_t)sum.n_open > per * (size_t)B || sum.n_dead < 0 || (size_t)sum.n_dead > per * (size_t)B ||
         (size_t)sum.n_open + (size_t)sum.n_dead != per * (size_t)B)
         return fail(ctx, MIPX_EHIP, "tree: the device finish returned an inconsistent summary");
-    char *hp = S.h_fin + 128;
+    const auto fin = finish_block(t, per).view(S.h_fin);
     const bool tab = t->rule == 1;
-    mipx::OpenEntry *open = (mipx::OpenEntry *)(hp + (t->tab_bytes + 31) / 32 * 32);
-    int32_t *dead = (int32_t *)(open + per * (size_t)t->max_batch);
-    if (tab) HIP_TRY(ctx, hipMemcpyAsync(hp, tab_at(t, S.tabv).cl, t->tab_bytes, hipMemcpyDeviceToHost, t->st2));
+    mipx::OpenEntry *open = (mipx::OpenEntry *)fin.open;
+    if (tab) HIP_TRY(ctx, hipMemcpyAsync(fin.table, tab_at(t, S.tabv).cl, t->tab_bytes, hipMemcpyDeviceToHost, t->st2));
     t->tab_host = S.tabv;   // launches from now on read the table as of this step
     if (sum.n_open > 0)
         HIP_TRY(ctx, hipMemcpyAsync(open, S.d_open, (size_t)sum.n_open * sizeof(mipx::OpenEntry), hipMemcpyDeviceToHost, t->st2));
     if (sum.n_dead > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(dead, S.d_dead, (size_t)sum.n_dead * 4, hipMemcpyDeviceToHost, t->st2));
+        HIP_TRY(ctx, hipMemcpyAsync(fin.dead, S.d_dead, (size_t)sum.n_dead * 4, hipMemcpyDeviceToHost, t->st2));
     if (sum.n_deferred > 0)   // the nodes that filed probe requests: everything the host loop reads per node
-        HIP_TRY(ctx, hipMemcpyAsync(S.h_pack, S.d_pack, S.pack_bytes, hipMemcpyDeviceToHost, t->st2));
+        HIP_TRY(ctx, hipMemcpyAsync(S.h_pack, S.d_pack, S.pack.bytes(), hipMemcpyDeviceToHost, t->st2));
     HIP_TRY(ctx, hipStreamSynchronize(t->st2));
     if (sum.n_deferred > 0) {
-        const int32_t asked = *(const int32_t *)(S.h_pack + S.ask_off);
+        const auto hv = S.pack.view((const char *)S.h_pack);
+        const int32_t asked = *hv.ask_count;
         if (asked < 1 || asked > kAskCap) return fail(ctx, MIPX_EHIP, "tree: the device finish deferred nodes without a request list");
-        const mipx::ScoreArgs::Ask *ask = (const mipx::ScoreArgs::Ask *)(S.h_pack + S.ask_off + 16);
+        const Ask *ask = (const Ask *)hv.ask;
         for (int32_t q = 0; q < asked; q++) deferred.push_back(ask[q].node);
         std::sort(deferred.begin(), deferred.end());
         deferred.erase(std::unique(deferred.begin(), deferred.end()), deferred.end());
         if ((int)deferred.size() != sum.n_deferred) return fail(ctx, MIPX_EHIP, "tree: deferred nodes and request list disagree");
     }
     t->phase_ms[1] += std::chrono::duration<double, std::milli>(now() - tp).count(); tp = now();
-    if (tab) table_snapshot(t, hp);
+    if (tab) table_snapshot(t, fin.table);
     // the new open nodes, in the order the host loop created them (chain by chain, level by level, left
     // then right)
     const bool defer_push = t->use_bq && t->search == 0;
@@ -1553,7 +1546,7 @@ int tree_finish_fast(mipx_tree *t, StepBuf &S, const mipx::FinishSummary &sum, s
     }
     if (defer_push) t->bq.push_many(t->pend.data(), t->pend.size());
     // rows free again: the budget rows that hold no open node, the batch's own rows
-    t->free_slots.insert(t->free_slots.end(), dead, dead + sum.n_dead);
+    t->free_slots.insert(t->free_slots.end(), fin.dead, fin.dead + sum.n_dead);
     if (deferred.empty()) {
         t->free_slots.insert(t->free_slots.end(), S.slots.begin(), S.slots.begin() + B);
     } else {    // (a deferred node's row feeds its children: the host part releases it)
@@ -1575,7 +1568,7 @@ int tree_finish_fast(mipx_tree *t, StepBuf &S, const mipx::FinishSummary &sum, s
     // anchor mode: the root's optimal tableau (a root that needed no probe comes this way)
     if (t->anchor_mode && !t->anchor_set && S.ids[0] == 0 && (deferred.empty() || deferred[0] != 0)) {
         int32_t st0 = -1;
-        int rc = tree_d2h(t, &st0, S.d_status, 4);
+        int rc = tree_d2h(t, &st0, S.d.status, 4);
         if (rc) return rc;
         if (st0 == 0) {
             std::vector<int8_t> rootv((size_t)t->n + t->m);
@@ -1589,477 +1582,482 @@ int tree_finish_fast(mipx_tree *t, StepBuf &S, const mipx::FinishSummary &sum, s
     return MIPX_OK;
 }
 
-// Second half: wait for that batch only, then the reference's bookkeeping and the children.
-int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
-    mipx_ctx *ctx = t->ctx;
-    const int n = t->n, nv = t->n + t->m;
-    const double inf = std::numeric_limits<double>::infinity();
-    hipStream_t st = ctx->stream;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms_since = [&](std::chrono::steady_clock::time_point t0) {
-        return std::chrono::duration<double, std::milli>(now() - t0).count();
-    };
-    auto tp = now();
-    const int B = S.B;
-    if (!S.in_flight || B == 0) return MIPX_OK;
-    S.in_flight = false;
-    const std::vector<int64_t> &ids = S.ids;
-    const std::vector<int32_t> &slots = S.slots;
-    int rc = MIPX_OK;
-    if (t->cuts && (rc = tree_cut_rounds(t, S))) return rc;
-    HIP_TRY(ctx, hipEventSynchronize(S.done));
-    {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, S.e0, S.e1) == hipSuccess) t->kernel_ms += ms;
-    }
-    if (S.heur_n > 0 && (rc = heur_step_collect(t, S))) return rc;   // (primal heuristic: its incumbent prunes this step's nodes)
-    // The nodes this function finishes, in order.  The whole batch: the nodes without probe requests first,
-    // then those with (each group in batch order) -- the order in which the device finish and the host part
-    // below share a step, so that both ways end with the same table, ids and queue.  Device finish: only
-    // the nodes it deferred (they filed probe requests).
+// ---- second half of a step on the host: tree_finish and its phases ------------------------------------------
+// What crosses the phases of one host finish.
+struct FinishWork {
+    using Clock = std::chrono::steady_clock;
+    StepBuf &S;
+    const bool overlapped;   // a step is in flight on the main stream: probes and re-scoring go to the side stream
+    Clock::time_point tp = Clock::now();     // start of the span the next phase_ms[] slot is charged with
+    step_layout::StepPack::View<char> h{};   // the host copy of the packed read-back
+    // The nodes this finish handles, in order.  The whole batch: the nodes without probe requests first, then those
+    // with (each group in batch order) -- the order in which the device finish and the host part share a step, so that
+    // both ways end with the same table, ids and queue.  partial (device finish): only the nodes it deferred.
     std::vector<int> todo;
     bool partial = false;
+    std::vector<uint8_t> prop_inf;           // bound propagation: the nodes it found infeasible
+    int64_t prop_asks = 0, total = 0;        // probe requests in the packed list: of those nodes, of the todo nodes
+    std::vector<int32_t> pair_pos, pair_var, pair_slot, pst;   // the probes: parent position, variable, row; LP status
+    std::vector<double> xrow, pobj;                            // x of the probed variables; the probes' objectives
+    int incumbent_pos = -1;
+    std::vector<DfEntry> df_recs, df_infs;   // (dual function: this step's solved and infeasible nodes)
+    static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+    void charge(double &slot) { slot += ms_since(tp); tp = Clock::now(); }
+    // The node at position pos (level pos / B) was followed in place by a dive child at pos + B: it counts when its
+    // LP was solved and it needs no strong-branching initialisation of its own (else it is dropped and queued like
+    // any other child).  The decision taken after pos is dvar[pos].
+    bool dived(int pos) const { return pos < S.dive * S.B && h.dvar[pos] >= 0 && h.status[pos + S.B] >= 0 && h.nprobe[pos + S.B] == 0; }
+};
+
+// The pool make_children writes its rows into: the node pool or the probe pool.
+struct ChildDst { double *l, *u; int8_t *v; int32_t *ncut, *ids; };
+
+// A branching list (step_layout::PairList) of `count` parents staged at dp, then make_children over it on `cs`: two
+// children per parent, from the step's outputs and the parents' pool rows into rows `child` of dst.  hp: pinned
+// staging, filled here and sent as one copy; null: four copies straight from the vectors.
+int launch_children(mipx_tree *t, StepBuf &S, hipStream_t cs, int count, const std::vector<int32_t> &slot,
+                    const std::vector<int32_t> &pos, const std::vector<int32_t> &var, const std::vector<int32_t> &child,
+                    int32_t *hp, int32_t *dp, const ChildDst &dst) {
+    mipx_ctx *ctx = t->ctx;
+    const step_layout::PairList lay((size_t)count);
+    const size_t c4 = (size_t)count * 4;   // bytes of a list of one entry per parent
+    const auto d = lay.view(dp);
+    if (hp) {
+        const auto s = lay.view(hp);
+        std::memcpy(s.parent_slot, slot.data(), c4); std::memcpy(s.parent_pos, pos.data(), c4);
+        std::memcpy(s.var, var.data(), c4); std::memcpy(s.child_slot, child.data(), 2 * c4);
+        HIP_TRY(ctx, hipMemcpyAsync(dp, hp, lay.bytes(), hipMemcpyHostToDevice, cs));
+    } else {
+        HIP_TRY(ctx, hipMemcpyAsync(d.parent_slot, slot.data(), c4, hipMemcpyHostToDevice, cs));
+        HIP_TRY(ctx, hipMemcpyAsync(d.parent_pos, pos.data(), c4, hipMemcpyHostToDevice, cs));
+        HIP_TRY(ctx, hipMemcpyAsync(d.var, var.data(), c4, hipMemcpyHostToDevice, cs));
+        HIP_TRY(ctx, hipMemcpyAsync(d.child_slot, child.data(), 2 * c4, hipMemcpyHostToDevice, cs));
+    }
+    mipx::ChildArgs ca;
+    ca.n = t->n; ca.m = t->m; ca.count = count;
+    ca.src_l = t->pool_l; ca.src_u = t->pool_u; ca.x = S.d_x; ca.vstat = S.d_vout;
+    ca.parent_slot = d.parent_slot; ca.parent_pos = d.parent_pos; ca.var = d.var; ca.child_slot = d.child_slot;
+    ca.dst_l = dst.l; ca.dst_u = dst.u; ca.dst_v = dst.v;
+    if (t->cuts) {  // a child has its parent's rows, cuts included (base_node.py:602-606)
+        ca.mstride = t->mrows; ca.kc = t->kc;
+        ca.src_ncut = S.w_ncut; ca.src_ids = S.w_ids; ca.dst_ncut = dst.ncut; ca.dst_ids = dst.ids;
+    }
+    hipLaunchKernelGGL(mipx::make_children, dim3(2 * count), dim3(256), 0, cs, ca);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
+// Phase 1: wait for the batch, then everything the host reads per node.  done: the device finished the whole step.
+int finish_collect(mipx_tree *t, FinishWork &W, bool &done) {
+    mipx_ctx *ctx = t->ctx; StepBuf &S = W.S;
+    const int B = S.B;
+    int rc = MIPX_OK;
+    done = false;
+    if (t->cuts && (rc = tree_cut_rounds(t, S))) return rc;
+    HIP_TRY(ctx, hipEventSynchronize(S.done));
+    float kms = 0.f;
+    if (hipEventElapsedTime(&kms, S.e0, S.e1) == hipSuccess) t->kernel_ms += kms;
+    if (S.heur_n > 0 && (rc = heur_step_collect(t, S))) return rc;   // (primal heuristic: its incumbent prunes this step's nodes)
     if (S.fast) {
-        mipx::FinishSummary *hs = (mipx::FinishSummary *)S.h_fin;
+        mipx::FinishSummary *hs = (mipx::FinishSummary *)finish_block(t, 2 * (1 + (size_t)t->dive)).view(S.h_fin).summary;
         if ((rc = tree_d2h(t, hs, S.d_sum, sizeof(mipx::FinishSummary)))) return rc;
         if (!hs->host_path) {
-            if ((rc = tree_finish_fast(t, S, *hs, todo))) return rc;
-            if (todo.empty()) return MIPX_OK;
-            partial = true;    // (the pack came with the lists)
+            if ((rc = tree_finish_fast(t, S, *hs, W.todo))) return rc;
+            if (W.todo.empty()) { done = true; return MIPX_OK; }
+            W.partial = true;    // (the pack came with the lists)
         } else {
-            // more probe requests than the compact list holds: the host finishes the whole step; the rows
-            // handed out for its children come back
+            // more probe requests than the compact list holds: the host finishes the whole step; its children's rows come back
             t->free_slots.insert(t->free_slots.end(), S.budget.begin(), S.budget.end());
             S.budget.clear();
         }
     }
     // one copy (pinned destination) for everything the host reads per node
-    if (!partial && (rc = tree_d2h(t, S.h_pack, S.d_pack, S.pack_bytes))) return rc;
-    const int L = t->dive + 1;   // (the pack is laid out for the tree's dive depth: layout_pack)
-    const size_t MB = (size_t)t->max_batch, OB = (size_t)L * MB, DB = (size_t)(L > 1 ? L - 1 : 1) * MB;
-    double *obj = (double *)S.h_pack, *bval = obj + OB, *dval = bval + OB;
-    int32_t *status = (int32_t *)(dval + DB), *bidx = status + OB, *mipf = bidx + OB, *nprobe = mipf + OB,
-            *npiv = nprobe + OB, *dvar = npiv + OB, *ddir = dvar + DB;
-    const int NB = (S.dive + 1) * B;  // output positions in use: the batch, then its dive children level by level
+    if (!W.partial && (rc = tree_d2h(t, S.h_pack, S.d_pack, S.pack.bytes()))) return rc;
+    W.h = S.pack.view(S.h_pack);   // (laid out for the tree's dive depth: layout_pack)
+    int32_t *status = W.h.status, *nprobe = W.h.nprobe;
     // bound propagation: a node it found infeasible is a node whose LP ended primal infeasible, whatever the LP on
     // its unchanged row returned -- no probes, no children, and its plunge children are dropped
-    std::vector<uint8_t> prop_inf;
-    int64_t prop_asks = 0;   // probe requests of those nodes in the packed list
     if (S.prop_n > 0) {
-        if ((rc = prop_step_collect(t, S, prop_inf))) return rc;
+        if ((rc = prop_step_collect(t, S, W.prop_inf))) return rc;
         for (int k = 0; k < B; k++) {
-            if (!prop_inf[(size_t)k]) continue;
-            prop_asks += nprobe[k];
+            if (!W.prop_inf[(size_t)k]) continue;
+            W.prop_asks += nprobe[k];
             status[k] = 1;
             nprobe[k] = 0;
-            if (S.dive > 0) dvar[k] = -1;
+            if (S.dive > 0) W.h.dvar[k] = -1;
         }
     }
-    // The node at position pos (level pos / B) was followed in place by a dive child at pos + B: it
-    // counts when its LP was solved and it needs no strong-branching initialisation of its own (else
-    // it is dropped and queued like any other child).  The decision taken after pos is dvar[pos].
-    auto dived = [&](int pos) {
-        return pos < S.dive * B && dvar[pos] >= 0 && status[pos + B] >= 0 && nprobe[pos + B] == 0;
+    if (!W.partial) {
+        for (int k = 0; k < B; k++)
+            if (nprobe[k] == 0) W.todo.push_back(k);
+        for (int k = 0; k < B; k++)
+            if (nprobe[k] != 0) W.todo.push_back(k);
+    }
+    t->lps += (int64_t)W.todo.size();
+    for (int k : W.todo) t->pivots += W.h.npiv[k];
+    W.charge(t->phase_ms[1]);
+    return MIPX_OK;
+}
+
+// Phase 2 (pseudo costs): the strong-branching probes the todo nodes asked for -- request list, probe records,
+// truncated LPs, results.
+int finish_probes(mipx_tree *t, FinishWork &W) {
+    mipx_ctx *ctx = t->ctx; StepBuf &S = W.S;
+    const int B = S.B, n = t->n;
+    const int32_t *nprobe = W.h.nprobe;
+    int rc = MIPX_OK;
+    for (int k : W.todo) W.total += nprobe[k];
+    auto request = [&](int pos, int var, double x) {   // one probe pair: under the node at pos, on var with value x
+        W.pair_pos.push_back(pos); W.pair_slot.push_back(S.slots[pos]); W.pair_var.push_back(var); W.xrow.push_back(x);
     };
-    if (!partial) {
-        for (int k = 0; k < B; k++)
-            if (nprobe[k] == 0) todo.push_back(k);
-        for (int k = 0; k < B; k++)
-            if (nprobe[k] != 0) todo.push_back(k);
+    // a step in flight on the main stream: the probes go to the side stream (K1b streams slabs of its own there)
+    hipStream_t ps = W.overlapped ? t->st2 : ctx->stream;
+    if (W.total > 0) {
+        if (2 * W.total > t->probe_cap) return fail(ctx, MIPX_ENOMEM, "tree: probe pool exhausted");
+        // The probe requests came with the packed read-back (K4 writes one compact entry per request); only a step
+        // with more than kAskCap of them -- the ramp-up -- reads the per-node lists and solutions in bulk.
+        const int32_t asked = *W.h.ask_count;
+        if (asked == W.total + W.prop_asks && asked <= kAskCap) {
+            const Ask *ask = (const Ask *)W.h.ask;
+            std::vector<Ask> es(ask, ask + asked);
+            std::sort(es.begin(), es.end(), [](const Ask &a, const Ask &b) { return a.node < b.node || (a.node == b.node && a.k < b.k); });
+            for (const Ask &e : es)
+                if (W.prop_inf.empty() || !W.prop_inf[(size_t)e.node]) request(e.node, t->int_idx[e.k], e.x);
+        } else {
+            std::vector<double> xall((size_t)B * n);
+            std::vector<int32_t> plist((size_t)B * t->n_int);
+            HIP_TRY(ctx, hipMemcpy(plist.data(), S.d_plist, plist.size() * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(xall.data(), S.d_x, xall.size() * 8, hipMemcpyDeviceToHost));
+            for (int k = 0; k < B; k++) {
+                const double *xk = xall.data() + (size_t)k * n;
+                for (int e = 0; e < nprobe[k]; e++) {
+                    const int var = t->int_idx[plist[(size_t)k * t->n_int + e]];
+                    request(k, var, xk[var]);
+                }
+            }
+        }
+        auto tq = FinishWork::Clock::now();
+        t->probe_ms[0] += FinishWork::ms_since(W.tp);
+        const int P = (int)W.pair_pos.size();
+        std::vector<int32_t> child_slot(2 * (size_t)P);
+        for (int c = 0; c < 2 * P; c++) child_slot[c] = c;
+        // (on the side stream when a step is in flight: the probes run beside its node LPs)
+        if ((rc = launch_children(t, S, ps, P, W.pair_slot, W.pair_pos, W.pair_var, child_slot, nullptr,
+                                  W.overlapped ? t->d_pairs2 : t->d_pairs, {t->pp_l, t->pp_u, t->pp_v, t->pp_ncut, t->pp_ids})))
+            return rc;
+        CutLaunch pcl;
+        if (t->cuts) {  // a probe has its parent's rows
+            const CutState cs((size_t)t->max_batch);
+            int maxc = 0;
+            for (int k = 0; k < B; k++) maxc = std::max(maxc, (int)*cs.field(S.h_cs, CutState::kRowsAfter, (size_t)k));
+            pcl.ncut = t->pp_ncut; pcl.ids = t->pp_ids; pcl.m_rows = t->m + maxc;
+        }
+        // truncated dual simplex on every probe (base_node.py:645-646)
+        if ((rc = launch_lp(t, 2 * P, t->pp_l, t->pp_u, t->pp_v, nullptr, t->sb_iters, t->pp_status, t->pp_obj, nullptr, nullptr,
+                            nullptr, nullptr, ps, nullptr, nullptr, t->cuts ? &pcl : nullptr)))
+            return rc;
+        W.pst.resize(2 * (size_t)P); W.pobj.resize(2 * (size_t)P);
+        t->probe_ms[1] += FinishWork::ms_since(tq); tq = FinishWork::Clock::now();
+        HIP_TRY(ctx, hipStreamSynchronize(ps));
+        t->probe_ms[2] += FinishWork::ms_since(tq); tq = FinishWork::Clock::now();
+        HIP_TRY(ctx, hipMemcpyAsync(t->h_pres, t->pp_obj, W.pobj.size() * 8, hipMemcpyDeviceToHost, t->st2));
+        if ((rc = tree_d2h(t, t->h_pres + (size_t)t->probe_cap * 8, t->pp_status, W.pst.size() * 4))) return rc;
+        std::memcpy(W.pobj.data(), t->h_pres, W.pobj.size() * 8);
+        std::memcpy(W.pst.data(), t->h_pres + (size_t)t->probe_cap * 8, W.pst.size() * 4);
+        t->probe_ms[3] += FinishWork::ms_since(tq);
+        t->probes += 2 * P;
     }
-    t->lps += (int64_t)todo.size();
-    for (int k : todo) t->pivots += npiv[k];
-    t->phase_ms[1] += ms_since(tp); tp = now();
+    W.charge(t->phase_ms[5]);
+    return MIPX_OK;
+}
 
-    // 3. pseudo costs: strong-branch initialisation + the update for the branch that made the node
-    if (t->rule == 1) {
-        int64_t total = 0;
-        for (int k : todo) total += nprobe[k];
-        std::vector<int32_t> plist, pair_pos, pair_var, pair_slot, child_slot;
-        std::vector<double> xrow;  // x of the probed variables
-        std::vector<int32_t> pst;
-        std::vector<double> pobj;
-        // a step in flight on the main stream: probes and re-scoring go to the side stream (K1b streams
-        // slabs of its own there)
-        const bool use_side = overlapped;
-        hipStream_t ps = use_side ? t->st2 : st;
-        if (total > 0) {
-            if (2 * total > t->probe_cap) return fail(ctx, MIPX_ENOMEM, "tree: probe pool exhausted");
-            // The probe requests came with the packed read-back (K4 writes one compact entry per
-            // request); only a step with more than kAskCap of them -- the ramp-up -- reads the
-            // per-node lists and solutions in bulk.
-            const int32_t asked = *(const int32_t *)(S.h_pack + S.ask_off);
-            if (asked == total + prop_asks && asked <= kAskCap) {
-                using Ask = mipx::ScoreArgs::Ask;
-                const Ask *ask = (const Ask *)(S.h_pack + S.ask_off + 16);
-                std::vector<Ask> es(ask, ask + asked);
-                std::sort(es.begin(), es.end(), [](const Ask &a, const Ask &b) {
-                    return a.node < b.node || (a.node == b.node && a.k < b.k);
-                });
-                for (const Ask &e : es) {
-                    if (!prop_inf.empty() && prop_inf[(size_t)e.node]) continue;
-                    pair_pos.push_back(e.node);
-                    pair_slot.push_back(slots[e.node]);
-                    pair_var.push_back(t->int_idx[e.k]);
-                    xrow.push_back(e.x);
-                }
-            } else {
-                std::vector<double> xall((size_t)B * n);
-                plist.resize((size_t)B * t->n_int);
-                HIP_TRY(ctx, hipMemcpy(plist.data(), S.d_plist, plist.size() * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(ctx, hipMemcpy(xall.data(), S.d_x, xall.size() * 8, hipMemcpyDeviceToHost));
-                for (int k = 0; k < B; k++) {
-                    const double *xk = xall.data() + (size_t)k * n;
-                    for (int e = 0; e < nprobe[k]; e++) {
-                        const int var = t->int_idx[plist[(size_t)k * t->n_int + e]];
-                        pair_pos.push_back(k);
-                        pair_slot.push_back(slots[k]);
-                        pair_var.push_back(var);
-                        xrow.push_back(xk[var]);
-                    }
-                }
-            }
-            auto tq = now();
-            t->probe_ms[0] += ms_since(tp);
-            const int P = (int)pair_pos.size();
-            child_slot.resize(2 * (size_t)P);
-            for (int c = 0; c < 2 * P; c++) child_slot[c] = c;
-            // d_pairs layout: [parent_slot | parent_pos | var | child_slot(2P)]
-            // (on the side stream when a step is in flight: the probes run beside its node LPs)
-            int32_t *dp = use_side ? t->d_pairs2 : t->d_pairs;
-            HIP_TRY(ctx, hipMemcpyAsync(dp, pair_slot.data(), (size_t)P * 4, hipMemcpyHostToDevice, ps));
-            HIP_TRY(ctx, hipMemcpyAsync(dp + P, pair_pos.data(), (size_t)P * 4, hipMemcpyHostToDevice, ps));
-            HIP_TRY(ctx, hipMemcpyAsync(dp + 2 * P, pair_var.data(), (size_t)P * 4, hipMemcpyHostToDevice, ps));
-            HIP_TRY(ctx, hipMemcpyAsync(dp + 3 * P, child_slot.data(), (size_t)P * 8, hipMemcpyHostToDevice, ps));
-            mipx::ChildArgs ca;
-            ca.n = n; ca.m = t->m; ca.count = P;
-            ca.src_l = t->pool_l; ca.src_u = t->pool_u;
-            ca.parent_slot = dp; ca.parent_pos = dp + P; ca.var = dp + 2 * P;
-            ca.x = S.d_x; ca.vstat = S.d_vout;
-            ca.dst_l = t->pp_l; ca.dst_u = t->pp_u; ca.dst_v = t->pp_v;
-            ca.child_slot = dp + 3 * P;
-            CutLaunch pcl;
-            if (t->cuts) {  // a probe is a child: it has its parent's rows, cuts included (base_node.py:602-606)
-                ca.mstride = t->mrows; ca.kc = t->kc;
-                ca.src_ncut = S.w_ncut; ca.src_ids = S.w_ids; ca.dst_ncut = t->pp_ncut; ca.dst_ids = t->pp_ids;
-                int maxc = 0;
-                for (int k = 0; k < B; k++) maxc = std::max(maxc, (int)S.h_cs[4 + 7 * MB + k]);
-                pcl.ncut = t->pp_ncut; pcl.ids = t->pp_ids; pcl.m_rows = t->m + maxc;
-            }
-            hipLaunchKernelGGL(mipx::make_children, dim3(2 * P), dim3(256), 0, ps, ca);
-            HIP_TRY(ctx, hipGetLastError());
-            // truncated dual simplex on every probe (base_node.py:645-646)
-            rc = launch_lp(t, 2 * P, t->pp_l, t->pp_u, t->pp_v, nullptr, t->sb_iters, t->pp_status,
-                           t->pp_obj, nullptr, nullptr, nullptr, nullptr, ps, nullptr, nullptr,
-                           t->cuts ? &pcl : nullptr);
-            if (rc) return rc;
-            pst.resize(2 * (size_t)P);
-            pobj.resize(2 * (size_t)P);
-            t->probe_ms[1] += ms_since(tq); tq = now();
-            HIP_TRY(ctx, hipStreamSynchronize(ps));
-            t->probe_ms[2] += ms_since(tq); tq = now();
-            HIP_TRY(ctx, hipMemcpyAsync(t->h_pres, t->pp_obj, pobj.size() * 8, hipMemcpyDeviceToHost, t->st2));
-            if ((rc = tree_d2h(t, t->h_pres + (size_t)t->probe_cap * 8, t->pp_status, pst.size() * 4))) return rc;
-            std::memcpy(pobj.data(), t->h_pres, pobj.size() * 8);
-            std::memcpy(pst.data(), t->h_pres + (size_t)t->probe_cap * 8, pst.size() * 4);
-            t->probe_ms[3] += ms_since(tq);
-            t->probes += 2 * P;
+// Phase 3 (pseudo costs): the table updates in the reference's order, the late samples to the device table, and
+// the re-scoring of the step with the updated table.
+int finish_table(mipx_tree *t, FinishWork &W) {
+    mipx_ctx *ctx = t->ctx; StepBuf &S = W.S;
+    const int B = S.B, n = t->n;
+    const double inf = std::numeric_limits<double>::infinity();
+    const auto &h = W.h;
+    const int32_t *status = h.status, *nprobe = h.nprobe; const double *obj = h.obj;
+    int rc = MIPX_OK;
+    // node by node; per node its probes (ascending integer index, left then right), then its own branch unless just initialised
+    size_t e = 0;
+    bool changed = false;
+    for (int k : W.todo) {   // (the requests are sorted by node: the nodes with requests come in that order)
+        if (!(status[k] == 0 || status[k] == 2)) continue;   // (not lp_feasible)
+        const NodeRec &nd = S.recs[k];
+        bool own_probed = false;
+        for (int q = 0; q < nprobe[k]; q++, e++) {
+            const int var = W.pair_var[e];
+            const double bv = W.xrow[e];
+            pc_update(t, var, 0, W.pst[2 * e], W.pobj[2 * e], obj[k], bv - std::floor(bv));
+            pc_update(t, var, 1, W.pst[2 * e + 1], W.pobj[2 * e + 1], obj[k], std::ceil(bv) - bv);
+            if (var == nd.b_idx) own_probed = true;
+            changed = true;
         }
-        t->phase_ms[5] += ms_since(tp); tp = now();
-        // table updates in the reference's order: node by node; per node its probes (ascending
-        // integer index, left then right), then its own branch unless just initialised
-        size_t e = 0;
-        bool changed = false;
-        for (int k : todo) {   // (the requests are sorted by node: the nodes with requests come in that order)
-            const bool lp_feasible = status[k] == 0 || status[k] == 2;
-            const NodeRec &nd = S.recs[k];
-            bool own_probed = false;
-            if (lp_feasible) {
-                for (int q = 0; q < nprobe[k]; q++, e++) {
-                    const int var = pair_var[e];
-                    const double bv = xrow[e];
-                    pc_update(t, var, 0, pst[2 * e], pobj[2 * e], obj[k], bv - std::floor(bv));
-                    pc_update(t, var, 1, pst[2 * e + 1], pobj[2 * e + 1], obj[k], std::ceil(bv) - bv);
-                    if (var == nd.b_idx) own_probed = true;
-                    changed = true;
-                }
-                // (a seed of a restart inherits no bound: its parent was not solved at this right-hand side)
-                if (nd.b_idx >= 0 && !own_probed && !(t->rs.on && nd.dual_bound == -inf)) {
-                    // variable_change: b_val - u[b_idx] (left) or l[b_idx] - b_val (right)
-                    const double vc = nd.b_dir == 0 ? nd.b_val - std::floor(nd.b_val)
-                                                    : std::ceil(nd.b_val) - nd.b_val;
-                    pc_update(t, nd.b_idx, nd.b_dir, status[k], obj[k], nd.dual_bound, vc);
-                    changed = true;
-                }
-                // the dive child: the update for the branch that made it -- like any node only if its
-                // own LP is feasible (pseudo_cost.py:42-43), and only where step 4 will accept the
-                // dive (the reference never creates that child under a pruned or integral parent)
-                // (a plunge: level by level, each child under the node before it)
-                for (int pos = k; dived(pos) && obj[pos] < t->primal && !mipf[pos] &&
-                                  (status[pos] == 0 || status[pos] == 2); pos += B) {
-                    const int cp = pos + B;
-                    if (!(status[cp] == 0 || status[cp] == 2)) break;
-                    const double vc = ddir[pos] == 0 ? dval[pos] - std::floor(dval[pos]) : std::ceil(dval[pos]) - dval[pos];
-                    pc_update(t, dvar[pos], ddir[pos], status[cp], obj[cp], obj[pos], vc);
-                    changed = true;
-                }
-            } else {
-                e += 0;
-            }
+        // (a seed of a restart inherits no bound: its parent was not solved at this right-hand side)
+        if (nd.b_idx >= 0 && !own_probed && !(t->rs.on && nd.dual_bound == -inf)) {
+            // variable_change: b_val - u[b_idx] (left) or l[b_idx] - b_val (right)
+            const double vc = nd.b_dir == 0 ? nd.b_val - std::floor(nd.b_val) : std::ceil(nd.b_val) - nd.b_val;
+            pc_update(t, nd.b_idx, nd.b_dir, status[k], obj[k], nd.dual_bound, vc);
+            changed = true;
         }
-        if (changed && !t->fast_ok) t->table_dirty = true;   // (device finish: the samples go to the device table below)
-        // re-score with the updated table: always in the sequential mode (the reference branches
-        // with the table its own node just updated); when steps overlap, only if probes created
-        // entries that the first scoring had to leave out (the wait covers the step in flight)
-        t->phase_ms[6] += ms_since(tp); tp = now();
-        if (t->fast_ok && !t->pend_samples.empty()) {
-            // the device holds the table: this step's samples reach it in the order they were applied here
-            const size_t cnt = t->pend_samples.size();
-            if (cnt > t->samples_cap) return fail(ctx, MIPX_ENOMEM, "tree: more pseudo-cost samples than the staging holds");
-            std::memcpy(S.h_samples, t->pend_samples.data(), cnt * sizeof(mipx::PcSample));
-            int32_t *hk = (int32_t *)(S.h_samples + t->samples_cap);   // (the keys again, densely, behind the samples)
-            for (size_t q = 0; q < cnt; q++) hk[q] = t->pend_samples[q].var_dir;
-            t->pend_samples.clear();
-            HIP_TRY(ctx, hipMemcpyAsync(S.d_skeys, hk, cnt * 4, hipMemcpyHostToDevice, t->stf));
-            // (onto the version at the tail of stf's queue: every later version is copied from it)
-            HIP_TRY(ctx, hipMemcpyAsync(S.d_samples, S.h_samples, cnt * sizeof(mipx::PcSample), hipMemcpyHostToDevice, t->stf));
-            const TabPtr tb = tab_at(t, t->tab_tail);
-            mipx::PcApplyArgs pa;
-            pa.n = n; pa.sum = nullptr; pa.count = (int)cnt; pa.samples = S.d_samples; pa.keys = S.d_skeys;
-            pa.cost_l = tb.cl; pa.cost_r = tb.cr; pa.has = tb.has; pa.times = tb.times; pa.own = tb.own;
-            hipLaunchKernelGGL(mipx::pc_apply, dim3(2 * n), dim3(64), 0, t->stf, pa);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipEventRecord(t->ev_tab[t->tab_tail], t->stf));
-            t->tab_late[t->tab_tail] = true;
-        }
-        if (t->fast_ok) t->tab_host = S.fast ? S.tabv : t->tab_tail;
-        if (changed && (!overlapped || total > 0)) {
-            // (device finish: the re-scoring reads copies of the host's snapshot + this step's updates, the device
-            // table itself only ever changes through pc_apply)
-            const bool side_tab = use_side || t->fast_ok;
-            double *cl = side_tab ? t->d_cost_l2 : t->d_cost_l, *cr = side_tab ? t->d_cost_r2 : t->d_cost_r;
-            uint8_t *ch = side_tab ? t->d_has2 : t->d_has;
-            HIP_TRY(ctx, hipMemcpyAsync(cl, t->cost_l.data(), (size_t)n * 8, hipMemcpyHostToDevice, ps));
-            HIP_TRY(ctx, hipMemcpyAsync(cr, t->cost_r.data(), (size_t)n * 8, hipMemcpyHostToDevice, ps));
-            HIP_TRY(ctx, hipMemcpyAsync(ch, t->has_entry.data(), (size_t)n, hipMemcpyHostToDevice, ps));
-            if (!side_tab) t->table_dirty = false;
-            if ((rc = launch_score(t, S, NB, side_tab, false, use_side ? 1 : 0))) return rc;
-            HIP_TRY(ctx, hipStreamSynchronize(ps));
-            if (!overlapped) {   // sequential mode: every node branches with the table its step just updated
-                if ((rc = tree_d2h(t, bidx, S.d_bidx, (size_t)NB * 4))) return rc;
-                if ((rc = tree_d2h(t, bval, S.d_bval, (size_t)NB * 8))) return rc;
-            } else {
-                // batches: only the nodes whose probes created the entries their first scoring had to leave out
-                // take the new choice; a node that asked for nothing branches as it was scored at the launch
-                // (what the device finish does with it, before the host ever sees the step)
-                std::vector<int32_t> nb((size_t)B);
-                std::vector<double> nvv((size_t)B);
-                if ((rc = tree_d2h(t, nb.data(), S.d_bidx, (size_t)B * 4))) return rc;
-                if ((rc = tree_d2h(t, nvv.data(), S.d_bval, (size_t)B * 8))) return rc;
-                for (int k : todo)
-                    if (nprobe[k] > 0) { bidx[k] = nb[(size_t)k]; bval[k] = nvv[(size_t)k]; }
-            }
+        // the dive child: the update for the branch that made it -- like any node only if its own LP is feasible
+        // (pseudo_cost.py:42-43), and only where the evaluation will accept the dive (the reference never creates that
+        // child under a pruned or integral parent); a plunge: level by level, each child under the node before it
+        for (int pos = k; W.dived(pos) && obj[pos] < t->primal && !h.mipf[pos] && (status[pos] == 0 || status[pos] == 2); pos += B) {
+            const int cp = pos + B;
+            if (!(status[cp] == 0 || status[cp] == 2)) break;
+            const double vc = h.ddir[pos] == 0 ? h.dval[pos] - std::floor(h.dval[pos]) : std::ceil(h.dval[pos]) - h.dval[pos];
+            pc_update(t, h.dvar[pos], h.ddir[pos], status[cp], obj[cp], obj[pos], vc);
+            changed = true;
         }
     }
+    if (changed && !t->fast_ok) t->table_dirty = true;   // (device finish: the samples go to the device table below)
+    W.charge(t->phase_ms[6]);
+    if (t->fast_ok && !t->pend_samples.empty()) {
+        // the device holds the table: this step's samples reach it in the order they were applied here
+        const size_t cnt = t->pend_samples.size();
+        if (cnt > t->samples_cap) return fail(ctx, MIPX_ENOMEM, "tree: more pseudo-cost samples than the staging holds");
+        std::memcpy(S.h_samples, t->pend_samples.data(), cnt * sizeof(mipx::PcSample));
+        int32_t *hk = (int32_t *)(S.h_samples + t->samples_cap);   // (the keys again, densely, behind the samples)
+        for (size_t q = 0; q < cnt; q++) hk[q] = t->pend_samples[q].var_dir;
+        t->pend_samples.clear();
+        HIP_TRY(ctx, hipMemcpyAsync(S.d_skeys, hk, cnt * 4, hipMemcpyHostToDevice, t->stf));
+        // (onto the version at the tail of stf's queue: every later version is copied from it)
+        HIP_TRY(ctx, hipMemcpyAsync(S.d_samples, S.h_samples, cnt * sizeof(mipx::PcSample), hipMemcpyHostToDevice, t->stf));
+        const TabPtr tb = tab_at(t, t->tab_tail);
+        mipx::PcApplyArgs pa;
+        pa.n = n; pa.sum = nullptr; pa.count = (int)cnt; pa.samples = S.d_samples; pa.keys = S.d_skeys;
+        pa.cost_l = tb.cl; pa.cost_r = tb.cr; pa.has = tb.has; pa.times = tb.times; pa.own = tb.own;
+        hipLaunchKernelGGL(mipx::pc_apply, dim3(2 * n), dim3(64), 0, t->stf, pa);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipEventRecord(t->ev_tab[t->tab_tail], t->stf));
+        t->tab_late[t->tab_tail] = true;
+    }
+    if (t->fast_ok) t->tab_host = S.fast ? S.tabv : t->tab_tail;
+    // re-score with the updated table: always in the sequential mode (the reference branches with the table its own
+    // node just updated); when steps overlap, only if probes created entries that the first scoring had to leave out
+    if (changed && (!W.overlapped || W.total > 0)) {
+        // (device finish: the re-scoring reads copies of the host's snapshot + this step's updates, the device table
+        // itself only ever changes through pc_apply)
+        const bool use_side = W.overlapped, side_tab = use_side || t->fast_ok;
+        hipStream_t ps = use_side ? t->st2 : ctx->stream;
+        const int NB = (S.dive + 1) * B;  // output positions in use: the batch, then its dive children level by level
+        double *cl = side_tab ? t->d_cost_l2 : t->d_cost_l, *cr = side_tab ? t->d_cost_r2 : t->d_cost_r;
+        uint8_t *ch = side_tab ? t->d_has2 : t->d_has;
+        HIP_TRY(ctx, hipMemcpyAsync(cl, t->cost_l.data(), (size_t)n * 8, hipMemcpyHostToDevice, ps));
+        HIP_TRY(ctx, hipMemcpyAsync(cr, t->cost_r.data(), (size_t)n * 8, hipMemcpyHostToDevice, ps));
+        HIP_TRY(ctx, hipMemcpyAsync(ch, t->has_entry.data(), (size_t)n, hipMemcpyHostToDevice, ps));
+        if (!side_tab) t->table_dirty = false;
+        if ((rc = launch_score(t, S, NB, side_tab, false, use_side ? 1 : 0))) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ps));
+        if (!W.overlapped) {   // sequential mode: every node branches with the table its step just updated
+            if ((rc = tree_d2h(t, h.bidx, S.d.bidx, (size_t)NB * 4))) return rc;
+            if ((rc = tree_d2h(t, h.bval, S.d.bval, (size_t)NB * 8))) return rc;
+        } else {
+            // batches: only the nodes whose probes created the entries their first scoring had to leave out take the new
+            // choice; a node that asked for nothing branches as it was scored at the launch (what the device finish does)
+            std::vector<int32_t> nb((size_t)B);
+            std::vector<double> nvv((size_t)B);
+            if ((rc = tree_d2h(t, nb.data(), S.d.bidx, (size_t)B * 4))) return rc;
+            if ((rc = tree_d2h(t, nvv.data(), S.d.bval, (size_t)B * 8))) return rc;
+            for (int k : W.todo)
+                if (nprobe[k] > 0) { h.bidx[k] = nb[(size_t)k]; h.bval[k] = nvv[(size_t)k]; }
+        }
+    }
+    return MIPX_OK;
+}
 
-    t->phase_ms[2] += ms_since(tp); tp = now();
-    // 4. the reference's _evaluate_node bookkeeping, node by node (a dive child right after its
-    //    parent: it was solved in the same workgroup)
-    std::vector<int32_t> &dive_slots = S.dive_slots;
+// One evaluated node at output position pos: the reference's _evaluate_node bookkeeping.  level 0: a node of the batch
+// (pool row `slot`); level p: a dive child.  Returns the id of the child that was solved in place by the dive (to be
+// evaluated next), or -1.  (Best first on the bucket queue: the step's pushes are collected in t->pend, queued together.)
+int64_t evaluate_node(mipx_tree *t, FinishWork &W, int64_t id, int pos, int32_t slot, int level, int depth, int32_t anchor, int &err) {
+    StepBuf &S = W.S;
+    const auto &h = W.h;
+    const int32_t *status = h.status; const double *obj = h.obj;
+    const double inf = std::numeric_limits<double>::infinity();
+    const bool rec = t->df.on, trec = t->tr.on, defer_push = t->use_bq && t->search == 0;
+    const CutState cs((size_t)t->max_batch);
+    t->evaluated++;
+    if (rec && status[pos] == 0) W.df_recs.push_back({pos, slot, id});
+    if (rec && status[pos] == 1) W.df_infs.push_back({pos, slot, id});
+    if (trec) t->tr.solved(id, status[pos], obj[pos], h.mipf[pos] != 0, h.nprobe[pos] > 0);
+    const bool lp_feasible = status[pos] == 0 || status[pos] == 2;
+    if (status[pos] == 2) t->unbounded = true;
+    int branched_on = -1;
+    int64_t dive_child = -1;
+    double leaf_value = lp_feasible ? obj[pos] : inf;
+    if (lp_feasible && obj[pos] < t->primal) {
+        const bool take_dive = W.dived(pos);
+        const int bvar = take_dive ? h.dvar[pos] : h.bidx[pos];  // a dive has already branched
+        if (h.mipf[pos]) {
+            t->primal = obj[pos];
+            W.incumbent_pos = pos;
+        } else if (bvar >= 0) {
+            if (t->free_slots.size() < 2) { err = fail(t->ctx, MIPX_ENOMEM, "tree: node pool exhausted"); return -1; }
+            branched_on = bvar;
+            const double xv = take_dive ? h.dval[pos] : h.bval[pos];
+            for (int dir = 0; dir < 2; dir++) {
+                NodeRec c;
+                c.dual_bound = obj[pos];
+                c.depth = depth + 1;
+                c.key = t->search == 0 ? c.dual_bound : -(double)c.depth;
+                c.b_idx = branched_on; c.b_dir = dir; c.b_val = xv;
+                c.born = (int32_t)t->steps;
+                c.anchor = anchor;
+                c.ncut = t->cuts ? *cs.field(S.h_cs, CutState::kRowsAfter, (size_t)pos) : 0;   // the rows of its parent, cuts included
+                c.slot = t->free_slots.back();
+                t->free_slots.pop_back();
+                S.br[(size_t)level].child.push_back(c.slot);
+#ifdef MIPX_HOSTPROF
+                const unsigned long long r0_ = __rdtsc();
+#endif
+                t->nodes.push_back(c);
+#ifdef MIPX_HOSTPROF
+                g_hp_rec += __rdtsc() - r0_;
+#endif
+                const int64_t cid = (int64_t)t->nodes.size() - 1;
+                if (rec) {
+                    t->df.parent.push_back(id); t->df.rec.push_back(-1); t->df.haschild.push_back(0);
+                    t->df.haschild[(size_t)id] = 1;
+                }
+                if (trec) t->tr.child(id);
+                if (take_dive && dir == h.ddir[pos]) dive_child = cid;  // already solved: never enters the queue
+                else if (defer_push) t->pend.push_back({c.key, cid});
+                else tree_push(t, cid);
+            }
+            S.br[(size_t)level].pos.push_back(pos);
+            S.br[(size_t)level].slot.push_back(slot);
+            S.br[(size_t)level].var.push_back(branched_on);
+            leaf_value = inf;  // no longer a leaf
+        }
+    }
+    if (branched_on < 0) t->closed_min = std::fmin(t->closed_min, leaf_value);
+    if (t->trace) {
+        t->tr_id.push_back(id); t->tr_status.push_back(status[pos]);
+        t->tr_bidx.push_back(branched_on); t->tr_obj.push_back(obj[pos]);
+        if (t->cuts)   // (the node's cut-round counters, in the order of the trace)
+            for (int f = 0; f <= CutState::kRowsAfter; f++) t->tr_cuts.push_back(*cs.field(S.h_cs, f, (size_t)pos));
+    }
+    return dive_child;
+}
+
+// Phase 4: the todo nodes evaluated one by one (a dive child right after its parent: it was solved in the same
+// workgroup), their children into the node table and the queue, the incumbent.
+int finish_evaluate(mipx_tree *t, FinishWork &W) {
+    StepBuf &S = W.S; const auto &h = W.h;
+    const int B = S.B, L = t->dive + 1;
     if ((int)S.br.size() < L) S.br.resize((size_t)L);
     for (auto &bl : S.br) { bl.pos.clear(); bl.slot.clear(); bl.var.clear(); bl.child.clear(); }
-    dive_slots.clear();
-    int incumbent_pos = -1;
-    // One evaluated node at output position pos.  level 0: a node of the batch (pool row
-    // `slot`); level 1: a dive child.  Returns the id of the child that was solved in place by
-    // the dive (to be evaluated next), or -1.
-    // (best first on the bucket queue: the pushes of the step are collected and queued together below)
+    S.dive_slots.clear();
     const bool defer_push = t->use_bq && t->search == 0;
     t->pend.clear();
-    const bool rec = t->df.on, trec = t->tr.on;
-    std::vector<DfEntry> df_recs, df_infs;   // (dual function: this step's solved and infeasible nodes)
-    auto evaluate = [&](int64_t id, int pos, int32_t slot, int level, int depth, int32_t anchor, int &err) -> int64_t {
-        t->evaluated++;
-        if (rec && status[pos] == 0) df_recs.push_back({pos, slot, id});
-        if (rec && status[pos] == 1) df_infs.push_back({pos, slot, id});
-        if (trec) t->tr.solved(id, status[pos], obj[pos], mipf[pos] != 0, nprobe[pos] > 0);
-        const bool lp_feasible = status[pos] == 0 || status[pos] == 2;
-        if (status[pos] == 2) t->unbounded = true;
-        int branched_on = -1;
-        int64_t dive_child = -1;
-        double leaf_value = lp_feasible ? obj[pos] : inf;
-        if (lp_feasible && obj[pos] < t->primal) {
-            const bool take_dive = dived(pos);
-            const int bvar = take_dive ? dvar[pos] : bidx[pos];  // a dive has already branched
-            if (mipf[pos]) {
-                t->primal = obj[pos];
-                incumbent_pos = pos;
-            } else if (bvar >= 0) {
-                if (t->free_slots.size() < 2) {
-                    err = fail(ctx, MIPX_ENOMEM, "tree: node pool exhausted");
-                    return -1;
-                }
-                branched_on = bvar;
-                const double xv = take_dive ? dval[pos] : bval[pos];
-                for (int dir = 0; dir < 2; dir++) {
-                    NodeRec c;
-                    c.dual_bound = obj[pos];
-                    c.depth = depth + 1;
-                    c.key = t->search == 0 ? c.dual_bound : -(double)c.depth;
-                    c.b_idx = branched_on; c.b_dir = dir; c.b_val = xv;
-                    c.born = (int32_t)t->steps;
-                    c.anchor = anchor;
-                    c.ncut = t->cuts ? S.h_cs[4 + 7 * MB + pos] : 0;   // the rows of its parent, cuts included
-                    c.slot = t->free_slots.back();
-                    t->free_slots.pop_back();
-                    S.br[(size_t)level].child.push_back(c.slot);
-#ifdef MIPX_HOSTPROF
-                    const unsigned long long r0_ = __rdtsc();
-#endif
-                    t->nodes.push_back(c);
-#ifdef MIPX_HOSTPROF
-                    g_hp_rec += __rdtsc() - r0_;
-#endif
-                    const int64_t cid = (int64_t)t->nodes.size() - 1;
-                    if (rec) {
-                        t->df.parent.push_back(id); t->df.rec.push_back(-1); t->df.haschild.push_back(0);
-                        t->df.haschild[(size_t)id] = 1;
-                    }
-                    if (trec) t->tr.child(id);
-                    if (take_dive && dir == ddir[pos]) {
-                        dive_child = cid;  // already solved: never enters the queue
-                    } else if (defer_push) {
-                        t->pend.push_back({c.key, cid});
-                    } else {
-                        tree_push(t, cid);
-                    }
-                }
-                S.br[(size_t)level].pos.push_back(pos);
-                S.br[(size_t)level].slot.push_back(slot);
-                S.br[(size_t)level].var.push_back(branched_on);
-                leaf_value = inf;  // no longer a leaf
-            }
-        }
-        if (branched_on < 0) t->closed_min = std::fmin(t->closed_min, leaf_value);
-        if (t->trace) {
-            t->tr_id.push_back(id); t->tr_status.push_back(status[pos]);
-            t->tr_bidx.push_back(branched_on); t->tr_obj.push_back(obj[pos]);
-            if (t->cuts)   // (the node's cut-round counters, in the order of the trace)
-                for (int f = 0; f < 8; f++) t->tr_cuts.push_back(S.h_cs[4 + (size_t)f * MB + pos]);
-        }
-        return dive_child;
-    };
-    for (int k : todo) {
+    for (int k : W.todo) {
         int err = MIPX_OK;
         // (a chain reads ten result arrays at every level: more streams than the hardware prefetcher follows)
-        if (!partial && (k & 7) == 0 && k + 40 < B) {
+        if (!W.partial && (k & 7) == 0 && k + 40 < B) {
             for (int lv = 0; lv <= S.dive; lv++) {
                 const int pp = lv * B + k + 32;
-                __builtin_prefetch(&status[pp]); __builtin_prefetch(&obj[pp]); __builtin_prefetch(&mipf[pp]);
-                __builtin_prefetch(&bidx[pp]); __builtin_prefetch(&bval[pp]); __builtin_prefetch(&nprobe[pp]);
-                __builtin_prefetch(&npiv[pp]);
-                if (lv < S.dive) { __builtin_prefetch(&dvar[pp]); __builtin_prefetch(&ddir[pp]); __builtin_prefetch(&dval[pp]); }
+                __builtin_prefetch(&h.status[pp]); __builtin_prefetch(&h.obj[pp]); __builtin_prefetch(&h.mipf[pp]);
+                __builtin_prefetch(&h.bidx[pp]); __builtin_prefetch(&h.bval[pp]); __builtin_prefetch(&h.nprobe[pp]);
+                __builtin_prefetch(&h.npiv[pp]);
+                if (lv < S.dive) { __builtin_prefetch(&h.dvar[pp]); __builtin_prefetch(&h.ddir[pp]); __builtin_prefetch(&h.dval[pp]); }
             }
         }
-        int64_t cid = evaluate(ids[k], k, slots[k], 0, S.recs[k].depth, S.recs[k].anchor, err);
+        int64_t cid = evaluate_node(t, W, S.ids[k], k, S.slots[k], 0, S.recs[k].depth, S.recs[k].anchor, err);
         if (err) { if (defer_push) t->bq.push_many(t->pend.data(), t->pend.size()); return err; }
         for (int level = 1; cid >= 0; level++) {   // the plunge: every dive child right after its parent
             const int32_t cslot = t->nodes[cid].slot;
             const int pos = level * B + k;
-            t->lps++;
-            t->dives++;
-            t->pivots += npiv[pos];
-            const int64_t next = evaluate(cid, pos, cslot, level, S.recs[k].depth + level, S.recs[k].anchor, err);
+            t->lps++; t->dives++;
+            t->pivots += h.npiv[pos];
+            const int64_t next = evaluate_node(t, W, cid, pos, cslot, level, S.recs[k].depth + level, S.recs[k].anchor, err);
             if (err) { if (defer_push) t->bq.push_many(t->pend.data(), t->pend.size()); return err; }
-            dive_slots.push_back(cslot);  // its record row feeds its own children below
+            S.dive_slots.push_back(cslot);  // its record row feeds its own children (finish_children)
             t->nodes[cid].slot = -1;
             cid = next;
         }
     }
     if (defer_push) t->bq.push_many(t->pend.data(), t->pend.size());
-    if (incumbent_pos >= 0) {
-        // the last improving node of the batch holds the incumbent
-        if ((rc = tree_d2h(t, t->best_x.data(), S.d_x + (size_t)incumbent_pos * n, (size_t)n * 8))) return rc;
+    if (W.incumbent_pos >= 0) {   // the last improving node of the batch holds the incumbent
+        const int rc = tree_d2h(t, t->best_x.data(), S.d_x + (size_t)W.incumbent_pos * t->n, (size_t)t->n * 8);
+        if (rc) return rc;
         t->have_x = true;
     }
-    t->phase_ms[3] += ms_since(tp); tp = now();
+    W.charge(t->phase_ms[3]);
+    return MIPX_OK;
+}
+
+// Phase 5: the root's basis where a later solve starts from it, the children records on the device, the dual
+// function's records, then the evaluated nodes' rows are free again.
+int finish_children(mipx_tree *t, FinishWork &W) {
+    mipx_ctx *ctx = t->ctx; StepBuf &S = W.S;
+    hipStream_t st = ctx->stream;
+    const int nv = t->n + t->m, L = t->dive + 1;
+    const bool root_solved = S.ids[0] == 0 && W.h.status[0] == 0;
+    int rc = MIPX_OK;
     // anchor mode: the refactorisations of every later node start from the root's optimal tableau
     // (cut rounds: only a root that kept no cut rows has a basis of the shared rows alone)
-    if (t->anchor_mode && !t->anchor_set && ids[0] == 0 && status[0] == 0 && (!partial || todo[0] == 0) &&
-        !(t->cuts && S.h_cs[4 + 7 * MB] != 0)) {
+    if (t->anchor_mode && !t->anchor_set && root_solved && (!W.partial || W.todo[0] == 0) &&
+        !(t->cuts && *CutState((size_t)t->max_batch).field(S.h_cs, CutState::kRowsAfter) != 0)) {
         std::vector<int8_t> rootv(nv);
         HIP_TRY(ctx, hipMemcpy(rootv.data(), S.d_vout, (size_t)nv, hipMemcpyDeviceToHost));
-        const int arc = mipx_problem_set_anchor(t->prob, rootv.data());
-        if (arc) return arc;
+        if ((rc = mipx_problem_set_anchor(t->prob, rootv.data()))) return rc;
         t->anchor_set = true;
     }
     // tree record: the root's optimal basis codes, once (the warm start of mipx_tree_node_solve)
-    if (trec && !t->tr.have_root && ids[0] == 0 && status[0] == 0) {
+    if (t->tr.on && !t->tr.have_root && root_solved) {
         t->tr.root_v.resize(nv);
         if ((rc = tree_d2h(t, t->tr.root_v.data(), S.d_vout, (size_t)nv))) return rc;
         t->tr.have_root = true;
     }
-    // 5. children records on the device, then release the evaluated nodes' rows
-    const int P = (int)S.br[0].pos.size();
-    if (P > 0) {
-        // when steps overlap this runs on its own stream, beside the node LPs of the step in flight
-        // (it writes fresh pool rows only); the next launch waits for it
-        hipStream_t cs = overlapped ? t->st3 : st;
-        if (overlapped) HIP_TRY(ctx, hipStreamSynchronize(t->st3));  // h_pairs / d_pairs free again
-        auto children = [&](int cnt, const std::vector<int32_t> &cslot, const std::vector<int32_t> &cpos,
-                            const std::vector<int32_t> &cvar, const std::vector<int32_t> &cchild,
-                            int32_t *hp, int32_t *dp) -> int {
-            std::memcpy(hp, cslot.data(), (size_t)cnt * 4);
-            std::memcpy(hp + cnt, cpos.data(), (size_t)cnt * 4);
-            std::memcpy(hp + 2 * cnt, cvar.data(), (size_t)cnt * 4);
-            std::memcpy(hp + 3 * cnt, cchild.data(), (size_t)cnt * 8);
-            HIP_TRY(ctx, hipMemcpyAsync(dp, hp, (size_t)cnt * 20, hipMemcpyHostToDevice, cs));
-            mipx::ChildArgs ca;
-            ca.n = n; ca.m = t->m; ca.count = cnt;
-            ca.src_l = t->pool_l; ca.src_u = t->pool_u;
-            ca.parent_slot = dp; ca.parent_pos = dp + cnt; ca.var = dp + 2 * cnt;
-            ca.x = S.d_x; ca.vstat = S.d_vout;
-            ca.dst_l = t->pool_l; ca.dst_u = t->pool_u; ca.dst_v = t->pool_v;
-            ca.child_slot = dp + 3 * cnt;
-            if (t->cuts) {
-                ca.mstride = t->mrows; ca.kc = t->kc;
-                ca.src_ncut = S.w_ncut; ca.src_ids = S.w_ids; ca.dst_ncut = t->pool_ncut; ca.dst_ids = t->pool_ids;
-            }
-            hipLaunchKernelGGL(mipx::make_children, dim3(2 * cnt), dim3(256), 0, cs, ca);
-            HIP_TRY(ctx, hipGetLastError());
-            return MIPX_OK;
-        };
+    // when steps overlap the records are written on their own stream, beside the node LPs of the step in flight
+    // (fresh pool rows only); the next launch waits for it
+    hipStream_t cs = W.overlapped ? t->st3 : st;
+    if (!S.br[0].pos.empty()) {
+        if (W.overlapped) HIP_TRY(ctx, hipStreamSynchronize(t->st3));  // h_pairs / d_pairs free again
         // level by level on one stream: the record of a dive child exists before its children are derived
-        const size_t part = 5 * (size_t)t->max_batch;  // staging per level
+        const size_t part = step_layout::PairList((size_t)t->max_batch).bytes() / 4;  // staging per level
         for (int level = 0; level < L; level++) {
             const auto &bl = S.br[(size_t)level];
             if (bl.pos.empty()) break;   // (no branching at this level: none below it either)
-            if ((rc = children((int)bl.pos.size(), bl.slot, bl.pos, bl.var, bl.child, t->h_pairs + (size_t)level * part,
-                               t->d_pairs + (size_t)level * part)))
+            if ((rc = launch_children(t, S, cs, (int)bl.pos.size(), bl.slot, bl.pos, bl.var, bl.child, t->h_pairs + (size_t)level * part,
+                                      t->d_pairs + (size_t)level * part, {t->pool_l, t->pool_u, t->pool_v, t->pool_ncut, t->pool_ids})))
                 return rc;
         }
-        if (overlapped) {
+        if (W.overlapped) {
             HIP_TRY(ctx, hipEventRecord(t->ev_child, t->st3));
-            t->child_pending = true;
-            t->child_recorded = true;
+            t->child_pending = true; t->child_recorded = true;
         } else {
             HIP_TRY(ctx, hipStreamSynchronize(st));
         }
     }
-    if (rec) {   // the step's records, behind its children records (the dive children's rows hold their bounds)
-        hipStream_t cs = overlapped ? t->st3 : st;
-        if ((rc = df_step(t, S, cs, df_recs, df_infs))) return rc;
-        if (overlapped && !(df_recs.empty() && df_infs.empty())) {
+    if (t->df.on) {   // the step's records, behind its children records (the dive children's rows hold their bounds)
+        if ((rc = df_step(t, S, cs, W.df_recs, W.df_infs))) return rc;
+        if (W.overlapped && !(W.df_recs.empty() && W.df_infs.empty())) {
             HIP_TRY(ctx, hipEventRecord(t->ev_child, t->st3));   // (the next launch, and so the rows' reuse, waits)
-            t->child_pending = true;
-            t->child_recorded = true;
+            t->child_pending = true; t->child_recorded = true;
         }
     }
-    for (int32_t sl : dive_slots) t->free_slots.push_back(sl);
-    for (int k : todo) t->free_slots.push_back(slots[k]);
-    (void)nv;
-    t->phase_ms[4] += ms_since(tp);
+    for (int32_t sl : S.dive_slots) t->free_slots.push_back(sl);
+    for (int k : W.todo) t->free_slots.push_back(S.slots[k]);
+    W.charge(t->phase_ms[4]);
     return MIPX_OK;
+}
+
+// Second half: wait for that batch only, then the reference's bookkeeping and the children.
+int tree_finish(mipx_tree *t, StepBuf &S, bool overlapped) {
+    FinishWork W{S, overlapped};
+    if (!S.in_flight || S.B == 0) return MIPX_OK;
+    S.in_flight = false;
+    int rc = MIPX_OK; bool done = false;
+    if ((rc = finish_collect(t, W, done)) || done) return rc;
+    // pseudo costs: strong-branch initialisation + the update for the branch that made the node
+    if (t->rule == 1 && ((rc = finish_probes(t, W)) || (rc = finish_table(t, W)))) return rc;
+    W.charge(t->phase_ms[2]);
+    if ((rc = finish_evaluate(t, W))) return rc;
+    return finish_children(t, W);
 }
 
 // ---- the exchange between the ranks of one search (mipx_tree_set_comm) --------------------------------
@@ -2758,8 +2756,9 @@ int mipx_tree_create_ex(mipx_problem *p, const int32_t *int_idx, int n_int, cons
     rc |= dmalloc(ctx, &t->pool_v, cap * nv);
     rc |= dmalloc(ctx, &t->d_int_idx, (size_t)n_int);
     const size_t LC = (size_t)kMaxDive + 1;   // output levels the buffers are sized for
-    rc |= dmalloc(ctx, &t->d_pairs, 5 * (pc / 2 > LC * B ? pc / 2 : LC * B));   // (one part per dive level)
-    rc |= dmalloc(ctx, &t->d_pairs2, 5 * (pc / 2 > LC * B ? pc / 2 : LC * B));
+    const size_t pairs = step_layout::PairList(pc / 2 > LC * B ? pc / 2 : LC * B).bytes() / 4;   // (one part per dive level)
+    rc |= dmalloc(ctx, &t->d_pairs, pairs);
+    rc |= dmalloc(ctx, &t->d_pairs2, pairs);
     rc |= dmalloc(ctx, &t->d_cost_l2, n); rc |= dmalloc(ctx, &t->d_cost_r2, n); rc |= dmalloc(ctx, &t->d_has2, n);
     // The side streams carry short, latency-critical work (probes, re-scoring, child records) that
     // must overtake the 2 ms node-LP launch queued on the main stream.  HIP multiplexes the streams
@@ -2772,7 +2771,7 @@ int mipx_tree_create_ex(mipx_problem *p, const int32_t *int_idx, int n_int, cons
     if (hipStreamCreateWithPriority(&t->stf, hipStreamNonBlocking, prio_greatest) != hipSuccess) rc |= MIPX_EHIP;
     if (hipStreamCreateWithPriority(&t->st3, hipStreamNonBlocking, prio_greatest) != hipSuccess ||
         hipEventCreateWithFlags(&t->ev_child, hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc((void **)&t->h_pairs, 5 * ((size_t)kMaxDive + 1) * B * 4, hipHostMallocDefault) != hipSuccess) rc |= MIPX_EHIP;
+        hipHostMalloc((void **)&t->h_pairs, step_layout::PairList(LC * B).bytes(), hipHostMallocDefault) != hipSuccess) rc |= MIPX_EHIP;
     if (t->cuts) {
         const size_t M = (size_t)t->mrows, K = (size_t)t->kc, SR = (size_t)t->slab_rows;
         rc |= dmalloc(ctx, &t->store_pi, (size_t)t->store_cap * n); rc |= dmalloc(ctx, &t->store_pi0, (size_t)t->store_cap);
@@ -2792,7 +2791,7 @@ int mipx_tree_create_ex(mipx_problem *p, const int32_t *int_idx, int n_int, cons
             rc |= dmalloc(ctx, &S.slab_pi, B * SR * n); rc |= dmalloc(ctx, &S.slab_pi0, B * SR);
             rc |= dmalloc(ctx, &S.dump_T, B * M * n); rc |= dmalloc(ctx, &S.dump_vec, B * (n + 3 * M));
             rc |= dmalloc(ctx, &S.dump_idx, B * (2 * n + M));
-            if (hipHostMalloc((void **)&S.h_cs, (4 + 9 * B) * 4, hipHostMallocDefault) != hipSuccess) rc |= MIPX_EHIP;
+            if (hipHostMalloc((void **)&S.h_cs, CutState(B).bytes(), hipHostMallocDefault) != hipSuccess) rc |= MIPX_EHIP;
             if (!t->pipeline) break;   // steps do not overlap: one buffer set is in use
         }
     }
@@ -2801,8 +2800,7 @@ int mipx_tree_create_ex(mipx_problem *p, const int32_t *int_idx, int n_int, cons
         // per-node outputs have one row per output level: the batch, then its dive children level by
         // level (allocated for the deepest plunge, laid out for the depth in use: layout_pack)
         rc |= dmalloc(ctx, &S.d_iters, LC * B);
-        const size_t pack_cap = (LC * B * (2 * 8 + 5 * 4) + LC * B * (8 + 2 * 4) + 15) / 16 * 16 + 16 +
-                                (size_t)kAskCap * sizeof(mipx::ScoreArgs::Ask);
+        const size_t pack_cap = step_pack(t, 1 + kMaxDive).bytes();
         rc |= dmalloc(ctx, &S.d_pack, pack_cap);
         if (hipHostMalloc((void **)&S.h_pack, pack_cap, hipHostMallocDefault) != hipSuccess ||
             hipHostMalloc((void **)&S.h_slot, 2 * B * 4, hipHostMallocDefault) != hipSuccess) rc |= MIPX_EHIP;
@@ -2841,7 +2839,7 @@ int mipx_tree_create_ex(mipx_problem *p, const int32_t *int_idx, int n_int, cons
             if (hipEventCreateWithFlags(&t->ev_tab[v], hipEventDisableTiming) != hipSuccess) rc |= MIPX_EHIP;
         t->samples_cap = (size_t)t->probe_cap + LC * B;
         for (StepBuf &S : t->buf) {
-            const size_t par_bytes = 2 * B * 8 + (4 * B + per * B) * 4;
+            const size_t par_bytes = step_layout::ParentBlock(B, per).bytes();
             rc |= dmalloc(ctx, &S.d_par, par_bytes);
             rc |= dmalloc(ctx, &S.c_info, B); rc |= dmalloc(ctx, &S.c_cnt, 3 * B); rc |= dmalloc(ctx, &S.c_eval, 2 * B);
             rc |= dmalloc(ctx, &S.c_flag, B); rc |= dmalloc(ctx, &S.c_val, 3 * B);
@@ -2849,7 +2847,7 @@ int mipx_tree_create_ex(mipx_problem *p, const int32_t *int_idx, int n_int, cons
             rc |= dmalloc(ctx, &S.d_open, per * B); rc |= dmalloc(ctx, &S.d_dead, per * B);
             rc |= dmalloc(ctx, &S.d_samples, t->samples_cap);
             rc |= dmalloc(ctx, &S.d_skeys, t->samples_cap);
-            const size_t fin_bytes = 128 + (t->tab_bytes + 31) / 32 * 32 + per * B * (sizeof(mipx::OpenEntry) + 4);
+            const size_t fin_bytes = finish_block(t, per).bytes();
             if (hipHostMalloc((void **)&S.h_par, par_bytes, hipHostMallocDefault) != hipSuccess ||
                 hipHostMalloc((void **)&S.h_fin, fin_bytes, hipHostMallocDefault) != hipSuccess ||
                 hipHostMalloc((void **)&S.h_samples, t->samples_cap * (sizeof(mipx::PcSample) + 4), hipHostMallocDefault) != hipSuccess)

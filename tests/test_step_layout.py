@@ -1,0 +1,22 @@
+"""The step buffers' layouts (csrc/step_layout.h) against the sizes and offsets the engine used before they had
+one definition: tests/support/step_layout_check.cpp, built with the host C++ compiler alone (no HIP, no GPU)."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, 'tests', 'support', 'step_layout_check.cpp')
+INC = os.path.join(ROOT, 'simple_mip_solver_amd', 'csrc')
+
+
+def test_step_layouts_match_the_engine(tmp_path):
+    cxx = os.environ.get('CXX') or shutil.which('c++') or shutil.which('g++') or shutil.which('clang++')
+    if cxx is None:
+        pytest.fail('no host C++ compiler (c++, g++ or clang++) to build the layout check with')
+    exe = str(tmp_path / 'step_layout_check')
+    subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Wextra', '-Werror', '-I', INC, SRC, '-o', exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert ' 0 failed' in run.stdout, run.stdout
