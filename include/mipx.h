@@ -536,5 +536,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_restart.h" /* restart a recorded search at another right-hand side from its leaves */
 #include "mipx_heur.h"    /* primal heuristic: round, repair and lift LP points on the GPU */
 #include "mipx_prop.h"    /* node presolve: activity-based bound propagation on the GPU */
+#include "mipx_rcfix.h"   /* reduced-cost bound tightening from the node LPs' row duals on the GPU */
 
 #endif /* MIPX_H */

@@ -298,6 +298,20 @@ PROP_STATUS = {0: 'unchanged', 1: 'tightened', 2: 'infeasible'}
 DEFAULT_PROPAGATION_ROUNDS = 8
 PROPAGATION_TOL = 1e-6
 
+# ... and those of include/mipx_rcfix.h (reduced-cost bound tightening from the row duals), which mipx.h includes
+# (tests/test_reduced_cost_abi.py checks them against that header)
+_RCFIX_SIGNATURES = {
+    'mipx_reduced_cost_tighten_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _d, _d, _d] + [_vp] * 5),
+    'mipx_tree_set_reduced_cost': (_i, [_vp, _i]),
+    'mipx_tree_reduced_cost_stats': (_i, [_vp, _vp]),
+}
+RCFIX_SYMBOLS = list(_RCFIX_SIGNATURES)
+RCFIX_STATS_KEYS = ('nodes', 'tightened', 'cut_off', 'no_bound', 'bounds_changed', 'launches', 'reserved', 'kernel_us')
+RCFIX_STATUS = {0: 'unchanged', 1: 'tightened', 2: 'cut_off', 3: 'no_bound'}
+# the tolerances of the engine's runs: tol as the propagation's, dtol the reduced cost below which a column is skipped
+RCFIX_TOL = 1e-6
+RCFIX_DTOL = 1e-9
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -314,7 +328,7 @@ def lib():
                                       list(_CUTMIG_SIGNATURES.items()) + list(_DUALFN_SIGNATURES.items()) +
                                       list(_TREEREC_SIGNATURES.items()) + list(_CGLP_SIGNATURES.items()) +
                                       list(_RESTART_SIGNATURES.items()) + list(_HEUR_SIGNATURES.items()) +
-                                      list(_PROP_SIGNATURES.items())):
+                                      list(_PROP_SIGNATURES.items()) + list(_RCFIX_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -793,6 +807,30 @@ class Problem:
         self.ctx.check(rc, 'mipx_propagate_batch')
         return dict(l=lo, u=uo, status=status, changed=changed, rounds=rounds)
 
+    def reduced_cost_tighten_batch(self, l, u, y, integer_indices, cutoff, tol=RCFIX_TOL, dtol=RCFIX_DTOL, in_place=False):
+        """Reduced-cost bound tightening on host buffers (mipx_reduced_cost_tighten_batch, include/mipx_rcfix.h):
+        l, u (batch, n) boxes, y (batch, m) row duals (any vectors), cutoff an objective value no point above which
+        is of interest (None or infinite: every box ends with status no_bound).  in_place: the outputs are the
+        (converted) inputs themselves.  Returns dict of l, u (batch, n), z (batch), status (RCFIX_STATUS codes) and
+        changed (batch each)."""
+        n, m = self.n, self.m
+        l = np.ascontiguousarray(l, dtype=np.float64).reshape(-1, n)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, n)
+        B = l.shape[0]
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(B, m)
+        assert u.shape[0] == B, 'l and u hold the same number of boxes'
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        cutoff = np.inf if cutoff is None else float(cutoff)
+        if in_place:
+            lo, uo = l, u = l.copy(), u.copy()
+        else:
+            lo = np.zeros((B, n)); uo = np.zeros((B, n))
+        z = np.zeros(B); status = np.zeros(B, np.int32); changed = np.zeros(B, np.int32)
+        rc = lib().mipx_reduced_cost_tighten_batch(self._h, B, _ptr(l), _ptr(u), _ptr(y), _ptr(ii), len(ii), cutoff, float(tol),
+                                                   float(dtol), _ptr(lo), _ptr(uo), _ptr(z), _ptr(status), _ptr(changed))
+        self.ctx.check(rc, 'mipx_reduced_cost_tighten_batch')
+        return dict(l=lo, u=uo, z=z, status=status, changed=changed)
+
     def solve_batch_dev(self, B, d_l, d_u, d_vstat, max_iter, d_status, d_obj, d_x, d_y, d_vout,
                         d_iters, d_npiv):
         rc = lib().mipx_lp_solve_batch_dev(self._h, int(B), d_l, d_u, d_vstat, int(max_iter),
@@ -1162,6 +1200,19 @@ class Tree:
         out = np.zeros(8, np.int64)
         self.problem.ctx.check(lib().mipx_tree_propagation_stats(self._h, _ptr(out)), 'mipx_tree_propagation_stats')
         return dict(zip(PROP_STATS_KEYS, (int(v) for v in out)))
+
+    def set_reduced_cost(self, on=True):
+        """Tighten the bounds of every step's branching parents from the row duals of their node LPs and the
+        incumbent on the GPU, in place on their pool rows before their children are written
+        (mipx_tree_set_reduced_cost, include/mipx_rcfix.h)."""
+        self.problem.ctx.check(lib().mipx_tree_set_reduced_cost(self._h, 1 if on else 0), 'mipx_tree_set_reduced_cost')
+
+    def reduced_cost_stats(self):
+        """dict(nodes, tightened, cut_off, no_bound, bounds_changed, launches, reserved, kernel_us)
+        (mipx_tree_reduced_cost_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_reduced_cost_stats(self._h, _ptr(out)), 'mipx_tree_reduced_cost_stats')
+        return dict(zip(RCFIX_STATS_KEYS, (int(v) for v in out)))
 
     def set_cut_migration(self, rows):
         """Reserve the top `rows` rows of the cut store for the cut rows of nodes received from other ranks, so

@@ -125,7 +125,7 @@ class BranchAndBound(BaseAlgorithm):
                  logging=False, max_run_time=INF, initial_primal_bound=INF, frontier_batch=None,
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
-                 propagate=None, **kwargs):
+                 propagate=None, reduced_cost=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -202,7 +202,14 @@ class BranchAndBound(BaseAlgorithm):
         node inherit what was tightened.  A node the propagation proves infeasible is closed as a node whose LP
         was infeasible.  True takes at most 8 rounds per node, an int that many.  The optimum is the same; the
         nodes evaluated on the way differ.  Every step is then finished on the host.  Counters:
-        `propagation_stats`."""
+        `propagation_stats`.
+        reduced_cost (extension; needs frontier_batch and gomory_cuts=False, not with comm, dual_function or
+        tree_record, so not with restart; default None = off): reduced-cost bound tightening.  The node LPs also
+        write their row duals, and once the search holds an incumbent every node that branches has the bounds
+        of its integer columns tightened from its reduced costs and the incumbent's objective, one GPU workgroup
+        per node (include/mipx_rcfix.h), in place before its children are written: the whole subtree inherits
+        them.  The optimum is the same; the nodes evaluated on the way differ.  Every step is then finished on
+        the host.  Counters: `reduced_cost_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -276,6 +283,19 @@ class BranchAndBound(BaseAlgorithm):
             'propagate cannot be combined with tree_record: bounds rebuilt from a lineage would miss the propagated ones'
         self._propagate = propagate
         self.propagation_stats = None
+        assert reduced_cost is None or reduced_cost is True, 'reduced_cost is None or True'
+        assert reduced_cost is None or frontier_batch is not None, \
+            'reduced_cost needs frontier_batch (it runs on the pool rows of the native engine)'
+        assert reduced_cost is None or comm is None, 'reduced_cost cannot be combined with comm'
+        assert reduced_cost is None or kwargs.get('gomory_cuts', True) is False, \
+            'reduced_cost needs gomory_cuts=False: the tightening does not see the cut rows of a node'
+        assert reduced_cost is None or not dual_function, \
+            'reduced_cost cannot be combined with dual_function: a tightened bound depends on the right-hand side'
+        assert reduced_cost is None or not tree_record, \
+            'reduced_cost cannot be combined with tree_record (and so with restart): bounds rebuilt from a lineage ' \
+            'would miss the tightened ones'
+        self._reduced_cost = reduced_cost
+        self.reduced_cost_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -454,6 +474,8 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_heuristic(self._primal_heuristic)
             if self._propagate:
                 self._native.set_propagation(self._propagate)
+            if self._reduced_cost:
+                self._native.set_reduced_cost(True)
         st = None
         if self._comm is not None and not self._sharded:
             from simple_mip_solver_amd.parallel import shard_and_attach
@@ -515,6 +537,8 @@ class BranchAndBound(BaseAlgorithm):
             self.heuristic_stats = self._native.heuristic_stats()
         if self._propagate:
             self.propagation_stats = self._native.propagation_stats()
+        if self._reduced_cost:
+            self.reduced_cost_stats = self._native.reduced_cost_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')

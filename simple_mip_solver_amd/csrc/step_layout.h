@@ -99,6 +99,22 @@ struct PropOut {
     }
 };
 
+// Reduced-cost tightening of a step, levels x max_batch branching parents (level p's at p * max_batch ..), i32:
+// what goes up [slot | pos] (the parents' pool rows and output positions), what comes down [status | changed].
+struct RcOut {
+    size_t max_batch, slot, pos, status, changed, end;
+    RcOut(size_t levels, size_t max_batch_)
+        : max_batch(max_batch_), slot(0), pos(4 * levels * max_batch_), status(8 * levels * max_batch_),
+          changed(12 * levels * max_batch_), end(16 * levels * max_batch_) {}
+    size_t bytes() const { return end; }
+    size_t in_bytes() const { return status; }             // the lists, in front
+    size_t level(size_t p) const { return p * max_batch; } // first entry of level p in every field
+    template <class Base> struct View { Like<int32_t, Base> *slot, *pos, *status, *changed; };
+    template <class Base> View<Base> view(Base *b) const {
+        return {at<int32_t>(b, slot), at<int32_t>(b, pos), at<int32_t>(b, status), at<int32_t>(b, changed)};
+    }
+};
+
 // Branching list of count parents, i32: [parent_slot | parent_pos | var | child_slot (left, right per parent)].
 struct PairList {
     size_t parent_slot, parent_pos, var, child_slot, end;

@@ -25,6 +25,7 @@
 #include "restart_kernels.hip.h"
 #include "heur_kernels.hip.h"
 #include "prop_kernels.hip.h"
+#include "rcfix_kernels.hip.h"
 #include "cglp_kernels.hip.h"
 #include "step_layout.h"
 
@@ -303,6 +304,8 @@ struct StepBuf {
     bool df_timed = false;
     int heur_n = 0;   // primal heuristic: the points of this step it was launched on (0: none)
     int prop_n = 0;   // bound propagation: the nodes of this step it was launched on (0: none)
+    std::vector<int> rc_cnt;          // reduced-cost tightening: the parents it was launched on, per level, not yet
+    hipStream_t rc_stream = nullptr;  // collected (empty: none), and the stream the launches went to
     int B = 0;
     bool in_flight = false;
     double inflight_min = std::numeric_limits<double>::infinity();   // lowest inherited bound of the batch (exchange record)
@@ -400,6 +403,20 @@ struct PropState {
     hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
     int64_t nodes = 0, tightened = 0, infeasible = 0, changed = 0, rounds = 0, capped = 0;
     double us = 0.0;                 // device time of prop_bounds
+};
+
+// Reduced-cost tightening (include/mipx_rcfix.h): per step buffer the node LPs' row duals, the parents' lists going
+// up and the results coming down (step_layout::RcOut), and an event pair per level.
+constexpr int kRcLevels = 9;   // the batch and its plunge levels (1 + kMaxDive)
+struct RcState {
+    bool on = false;
+    int cap = 0;                     // nodes per level the step buffers are laid out for (the tree's max_batch)
+    double tol = 1e-6, dtol = 1e-9;
+    double *d_y[3] = {nullptr, nullptr, nullptr};   // kRcLevels x cap x m
+    int32_t *d_io[3] = {nullptr, nullptr, nullptr}, *h_io[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0[3][kRcLevels] = {}, e1[3][kRcLevels] = {};
+    int64_t nodes = 0, tightened = 0, cut_off = 0, no_bound = 0, changed = 0, launches = 0;
+    double us = 0.0;                 // device time of rc_tighten
 };
 
 struct mipx_tree {
@@ -532,6 +549,7 @@ struct mipx_tree {
     RestartRec rs;
     HeurState hr;
     PropState pg;
+    RcState rc;
     // cut migration (mipx_tree_set_cut_migration): the top cm_rows rows of the cut store take the cut rows
     // of nodes received from other ranks, filled in order by the migration code (host-side fill level)
     int64_t cm_rows = 0, cm_used = 0;
@@ -805,6 +823,92 @@ int prop_step_collect(mipx_tree *t, StepBuf &S, std::vector<uint8_t> &inf) {
 
 constexpr int kAskCap = 2048;  // probe requests per step carried in the packed read-back
 constexpr int kMaxDive = 8;    // dive children in a row per node (buffers are sized for it)
+
+// ---- reduced-cost tightening (include/mipx_rcfix.h) --------------------------------------------------------
+static_assert(kRcLevels == 1 + kMaxDive, "RcState keeps an event pair per level of a step");
+// One launch of rc_tighten over `batch` nodes in device memory, queued on `st` (d_slot: the rows of d_l, d_u the
+// nodes are, d_pos: their rows of d_y, or null for rows 0 .. batch - 1; d_l_out, d_u_out may be d_l, d_u; d_z may
+// be null).
+int rc_launch(const mipx_problem *p, hipStream_t st, int batch, const int32_t *d_slot, const int32_t *d_pos, const double *d_l,
+              const double *d_u, const double *d_y, const int32_t *d_int_idx, int n_int, double cutoff, double tol, double dtol,
+              double *d_l_out, double *d_u_out, double *d_z, int32_t *d_status, int32_t *d_changed) {
+    mipx_ctx *ctx = p->ctx;
+    if (p->m > mipx::kRcMax || p->n > mipx::kRcMax) return fail(ctx, MIPX_ETOOBIG, "reduced-cost tightening: more than 1024 rows or columns");
+    if (batch <= 0) return MIPX_OK;
+    mipx::RcArgs a;
+    a.m = p->m; a.n = p->n; a.n_int = n_int; a.cutoff = cutoff; a.tol = tol; a.dtol = dtol;
+    a.A = p->dA; a.b = p->db; a.c = p->dc; a.int_idx = d_int_idx; a.slot = d_slot; a.pos = d_pos;
+    a.l = d_l; a.u = d_u; a.y = d_y; a.l_out = d_l_out; a.u_out = d_u_out; a.z_out = d_z;
+    a.status_out = d_status; a.changed_out = d_changed;
+    hipLaunchKernelGGL(mipx::rc_tighten, dim3((unsigned)batch), dim3(mipx::kRcNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
+step_layout::RcOut rc_layout(const mipx_tree *t) { return {(size_t)kRcLevels, (size_t)t->rc.cap}; }
+
+// What the launches of S's last finish found, once they are done: the counters and the kernel's device time.
+int rc_step_collect(mipx_tree *t, StepBuf &S) {
+    if (S.rc_cnt.empty()) return MIPX_OK;
+    RcState &rs = t->rc;
+    mipx_ctx *ctx = t->ctx;
+    const int bi = (int)(&S - t->buf);
+    const step_layout::RcOut lay = rc_layout(t);
+    HIP_TRY(ctx, hipStreamSynchronize(S.rc_stream));
+    const int rc = tree_d2h(t, (char *)rs.h_io[bi] + lay.status, (const char *)rs.d_io[bi] + lay.status, lay.bytes() - lay.status);
+    if (rc) return rc;
+    const auto o = lay.view((const int32_t *)rs.h_io[bi]);
+    for (size_t level = 0; level < S.rc_cnt.size(); level++) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, rs.e0[bi][level], rs.e1[bi][level]) == hipSuccess) rs.us += 1000.0 * ms;
+        rs.launches++;
+        for (size_t k = lay.level(level), end = k + (size_t)S.rc_cnt[level]; k < end; k++) {
+            rs.nodes++;
+            rs.changed += o.changed[k];
+            if (o.status[k] == MIPX_RCFIX_TIGHTENED) rs.tightened++;
+            if (o.status[k] == MIPX_RCFIX_CUT_OFF) rs.cut_off++;
+            if (o.status[k] == MIPX_RCFIX_NO_BOUND) rs.no_bound++;
+        }
+    }
+    S.rc_cnt.clear();
+    return MIPX_OK;
+}
+
+// The branching parents of S's levels staged for the tightening: their (pool row, output position) lists in one
+// copy on `cs`, in front of the level-by-level launches (rc_level_launch).
+int rc_step_stage(mipx_tree *t, StepBuf &S, hipStream_t cs, int levels) {
+    RcState &rs = t->rc;
+    const int bi = (int)(&S - t->buf);
+    const step_layout::RcOut lay = rc_layout(t);
+    const auto h = lay.view(rs.h_io[bi]);
+    for (int level = 0; level < levels; level++) {
+        const auto &bl = S.br[(size_t)level];
+        if (bl.pos.empty()) break;
+        if (bl.pos.size() > (size_t)rs.cap) return fail(t->ctx, MIPX_ENOMEM, "tree: more branching parents in a level than the batch holds");
+        std::memcpy(h.slot + lay.level((size_t)level), bl.slot.data(), bl.slot.size() * 4);
+        std::memcpy(h.pos + lay.level((size_t)level), bl.pos.data(), bl.pos.size() * 4);
+    }
+    HIP_TRY(t->ctx, hipMemcpyAsync(rs.d_io[bi], rs.h_io[bi], lay.in_bytes(), hipMemcpyHostToDevice, cs));
+    S.rc_stream = cs;
+    return MIPX_OK;
+}
+
+// Level `level`'s `count` parents through rc_tighten on `cs`, in place on their pool rows.
+int rc_level_launch(mipx_tree *t, StepBuf &S, hipStream_t cs, int level, int count) {
+    RcState &rs = t->rc;
+    mipx_ctx *ctx = t->ctx;
+    const int bi = (int)(&S - t->buf);
+    const step_layout::RcOut lay = rc_layout(t);
+    const auto d = lay.view(rs.d_io[bi]);
+    const size_t off = lay.level((size_t)level);
+    HIP_TRY(ctx, hipEventRecord(rs.e0[bi][level], cs));
+    const int rc = rc_launch(t->prob, cs, count, d.slot + off, d.pos + off, t->pool_l, t->pool_u, rs.d_y[bi], t->d_int_idx, t->n_int,
+                             t->primal, rs.tol, rs.dtol, t->pool_l, t->pool_u, nullptr, d.status + off, d.changed + off);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(rs.e1[bi][level], cs));
+    S.rc_cnt.push_back(count);
+    return MIPX_OK;
+}
 
 // The step buffers (step_layout.h) at this tree's dimensions.  The element sizes the layouts take are the
 // kernels' types: a probe request, an open entry, and the summary in front of the table block at 128.
@@ -1310,7 +1414,7 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
                      !t->rs.on;   // (a restart's root is a seed: its row holds the source's root basis)
     rc = launch_lp(t, B, t->pool_l, t->pool_u, t->pool_v, S.d_slot, 0, S.d.status, S.d.obj,
                    S.d_x, S.d_vout, S.d_iters, S.d.npiv, nullptr, S.dive ? &S : nullptr, S.d_slot + B, nullptr,
-                   t->df.on ? S.df_y : nullptr);
+                   t->df.on ? S.df_y : t->rc.on ? t->rc.d_y[&S - t->buf] : nullptr);   // (the two exclude each other)
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(S.e1, st));
     if (S.fast) {
@@ -2017,11 +2121,16 @@ int finish_children(mipx_tree *t, FinishWork &W) {
     hipStream_t cs = W.overlapped ? t->st3 : st;
     if (!S.br[0].pos.empty()) {
         if (W.overlapped) HIP_TRY(ctx, hipStreamSynchronize(t->st3));  // h_pairs / d_pairs free again
+        // reduced-cost tightening: with an incumbent, every level's parents are tightened in place in front of the
+        // launch that copies their rows into their children (level p's parents: the rows level p - 1 just wrote)
+        const bool tighten = t->rc.on && std::isfinite(t->primal);
+        if (tighten && ((rc = rc_step_collect(t, S)) || (rc = rc_step_stage(t, S, cs, L)))) return rc;
         // level by level on one stream: the record of a dive child exists before its children are derived
         const size_t part = step_layout::PairList((size_t)t->max_batch).bytes() / 4;  // staging per level
         for (int level = 0; level < L; level++) {
             const auto &bl = S.br[(size_t)level];
             if (bl.pos.empty()) break;   // (no branching at this level: none below it either)
+            if (tighten && (rc = rc_level_launch(t, S, cs, level, (int)bl.pos.size()))) return rc;
             if ((rc = launch_children(t, S, cs, (int)bl.pos.size(), bl.slot, bl.pos, bl.var, bl.child, t->h_pairs + (size_t)level * part,
                                       t->d_pairs + (size_t)level * part, {t->pool_l, t->pool_u, t->pool_v, t->pool_ncut, t->pool_ids})))
                 return rc;
@@ -2031,6 +2140,7 @@ int finish_children(mipx_tree *t, FinishWork &W) {
             t->child_pending = true; t->child_recorded = true;
         } else {
             HIP_TRY(ctx, hipStreamSynchronize(st));
+            if (tighten && (rc = rc_step_collect(t, S))) return rc;
         }
     }
     if (t->df.on) {   // the step's records, behind its children records (the dive children's rows hold their bounds)
@@ -2963,6 +3073,18 @@ void mipx_tree_destroy(mipx_tree *t) {
             if (pg.e1[k]) (void)hipEventDestroy(pg.e1[k]);
         }
     }
+    {
+        RcState &rs = t->rc;
+        for (int k = 0; k < 3; k++) {
+            if (rs.d_y[k]) (void)hipFree(rs.d_y[k]);
+            if (rs.d_io[k]) (void)hipFree(rs.d_io[k]);
+            if (rs.h_io[k]) (void)hipHostFree(rs.h_io[k]);
+            for (int q = 0; q < kRcLevels; q++) {
+                if (rs.e0[k][q]) (void)hipEventDestroy(rs.e0[k][q]);
+                if (rs.e1[k][q]) (void)hipEventDestroy(rs.e1[k][q]);
+            }
+        }
+    }
     if (t->h_pairs) (void)hipHostFree(t->h_pairs);
     if (t->h_pres) (void)hipHostFree(t->h_pres);
     if (t->h_tab) (void)hipHostFree(t->h_tab);
@@ -3399,6 +3521,7 @@ int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps) {
     if (c && t->tr.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the tree record (mipx_tree_set_tree_record)");
     if (c && t->hr.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the primal heuristic (mipx_tree_set_heuristic)");
     if (c && t->pg.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the bound propagation (mipx_tree_set_propagation)");
+    if (c && t->rc.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the reduced-cost tightening (mipx_tree_set_reduced_cost)");
     t->comm = c;
     t->x_every = c ? every_steps : 0;
     if (!c) return MIPX_OK;
@@ -3780,3 +3903,4 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "restart_api.hip.h"
 #include "heur_api.hip.h"
 #include "prop_api.hip.h"
+#include "rcfix_api.hip.h"
