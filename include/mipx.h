@@ -537,5 +537,7 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_heur.h"    /* primal heuristic: round, repair and lift LP points on the GPU */
 #include "mipx_prop.h"    /* node presolve: activity-based bound propagation on the GPU */
 #include "mipx_rcfix.h"   /* reduced-cost bound tightening from the node LPs' row duals on the GPU */
+#include "mipx_lsearch.h" /* pair-move local search behind the primal heuristic on the GPU */
+#include "mipx_objstep.h" /* objective-step cutoff of the frontier engine */
 
 #endif /* MIPX_H */

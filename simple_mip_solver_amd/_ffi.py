@@ -312,6 +312,28 @@ RCFIX_STATUS = {0: 'unchanged', 1: 'tightened', 2: 'cut_off', 3: 'no_bound'}
 RCFIX_TOL = 1e-6
 RCFIX_DTOL = 1e-9
 
+# ... those of include/mipx_lsearch.h (the pair-move local search behind the primal heuristic), which mipx.h includes
+# (tests/test_local_search_abi.py checks them against that header)
+_LSEARCH_SIGNATURES = {
+    'mipx_pair_search_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _d, _i] + [_vp] * 5),
+    'mipx_tree_set_local_search': (_i, [_vp, _i]),
+    'mipx_tree_local_search_stats': (_i, [_vp, _vp]),
+}
+LSEARCH_SYMBOLS = list(_LSEARCH_SIGNATURES)
+LSEARCH_STATS_KEYS = ('points', 'improved', 'single_moves', 'pair_moves', 'capped', 'incumbents', 'reserved', 'kernel_us')
+LSEARCH_STATUS = {0: 'local_opt', 1: 'capped', 2: 'not_feasible', 3: 'skipped'}
+# moves per point that local_search=True / set_local_search(True) take at most
+DEFAULT_LOCAL_SEARCH_MOVES = 64
+
+# ... and those of include/mipx_objstep.h (the objective-step cutoff), which mipx.h includes
+# (tests/test_objective_step_abi.py checks them against that header)
+_OBJSTEP_SIGNATURES = {
+    'mipx_tree_set_objective_step': (_i, [_vp, _d]),
+    'mipx_tree_objective_step_stats': (_i, [_vp, _vp]),
+}
+OBJSTEP_SYMBOLS = list(_OBJSTEP_SIGNATURES)
+OBJSTEP_STATS_KEYS = ('closed_at_pop', 'left_unbranched', 'launches') + tuple('reserved%d' % k for k in range(3, 8))
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -328,7 +350,8 @@ def lib():
                                       list(_CUTMIG_SIGNATURES.items()) + list(_DUALFN_SIGNATURES.items()) +
                                       list(_TREEREC_SIGNATURES.items()) + list(_CGLP_SIGNATURES.items()) +
                                       list(_RESTART_SIGNATURES.items()) + list(_HEUR_SIGNATURES.items()) +
-                                      list(_PROP_SIGNATURES.items()) + list(_RCFIX_SIGNATURES.items())):
+                                      list(_PROP_SIGNATURES.items()) + list(_RCFIX_SIGNATURES.items()) +
+                                      list(_LSEARCH_SIGNATURES.items()) + list(_OBJSTEP_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -789,6 +812,28 @@ class Problem:
         self.ctx.check(rc, 'mipx_round_repair_batch')
         return dict(x=xo, obj=obj, status=status, moves=moves)
 
+    def pair_search_batch(self, x, l, u, integer_indices, tol=1e-9, max_moves=DEFAULT_LOCAL_SEARCH_MOVES, skip=None,
+                          in_place=False):
+        """The pair-move local search on host buffers (mipx_pair_search_batch, include/mipx_lsearch.h): x (batch, n)
+        feasible integral points, l, u the bounds (n each), skip an optional (batch,) mask.  in_place: the output is
+        the (converted) input itself.  Returns dict of x (batch, n), obj, status (LSEARCH_STATUS codes) and moves
+        (batch, 2: singles, pairs)."""
+        n = self.n
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n)
+        B = x.shape[0]
+        l, u = _arr(l, np.float64, n), _arr(u, np.float64, n)
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        sk = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8).reshape(B)
+        if in_place:
+            xo = x = x.copy()
+        else:
+            xo = np.zeros((B, n))
+        obj = np.zeros(B); status = np.zeros(B, np.int32); moves = np.zeros((B, 2), np.int32)
+        rc = lib().mipx_pair_search_batch(self._h, B, _ptr(x), _ptr(l), _ptr(u), _ptr(ii), len(ii), float(tol), int(max_moves),
+                                          _ptr(sk), _ptr(xo), _ptr(obj), _ptr(status), _ptr(moves))
+        self.ctx.check(rc, 'mipx_pair_search_batch')
+        return dict(x=xo, obj=obj, status=status, moves=moves)
+
     def propagate_batch(self, l, u, integer_indices, cutoff=None, tol=PROPAGATION_TOL, max_rounds=DEFAULT_PROPAGATION_ROUNDS):
         """Bound propagation on host buffers (mipx_propagate_batch, include/mipx_prop.h): l, u (batch, n) boxes,
         cutoff None or an objective value no point above which is of interest.  Returns dict of l, u (batch, n),
@@ -1213,6 +1258,31 @@ class Tree:
         out = np.zeros(8, np.int64)
         self.problem.ctx.check(lib().mipx_tree_reduced_cost_stats(self._h, _ptr(out)), 'mipx_tree_reduced_cost_stats')
         return dict(zip(RCFIX_STATS_KEYS, (int(v) for v in out)))
+
+    def set_local_search(self, max_moves=True):
+        """Run the pair-move local search behind the primal heuristic of every step, in place on its feasible points
+        (mipx_tree_set_local_search, include/mipx_lsearch.h; True: DEFAULT_LOCAL_SEARCH_MOVES moves per point at
+        most; 0 or False: off).  After set_heuristic."""
+        max_moves = DEFAULT_LOCAL_SEARCH_MOVES if max_moves is True else int(max_moves)
+        self.problem.ctx.check(lib().mipx_tree_set_local_search(self._h, max_moves), 'mipx_tree_set_local_search')
+
+    def local_search_stats(self):
+        """dict(points, improved, single_moves, pair_moves, capped, incumbents, reserved, kernel_us)
+        (mipx_tree_local_search_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_local_search_stats(self._h, _ptr(out)), 'mipx_tree_local_search_stats')
+        return dict(zip(LSEARCH_STATS_KEYS, (int(v) for v in out)))
+
+    def set_objective_step(self, step):
+        """Prune at one objective step below the incumbent (mipx_tree_set_objective_step, include/mipx_objstep.h):
+        the caller guarantees that the objectives of any two integer-feasible points differ by a multiple of step."""
+        self.problem.ctx.check(lib().mipx_tree_set_objective_step(self._h, float(step)), 'mipx_tree_set_objective_step')
+
+    def objective_step_stats(self):
+        """dict(closed_at_pop, left_unbranched, launches, reserved3 .. reserved7) (mipx_tree_objective_step_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_objective_step_stats(self._h, _ptr(out)), 'mipx_tree_objective_step_stats')
+        return dict(zip(OBJSTEP_STATS_KEYS, (int(v) for v in out)))
 
     def set_cut_migration(self, rows):
         """Reserve the top `rows` rows of the cut store for the cut rows of nodes received from other ranks, so

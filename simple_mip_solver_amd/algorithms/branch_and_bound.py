@@ -125,7 +125,7 @@ class BranchAndBound(BaseAlgorithm):
                  logging=False, max_run_time=INF, initial_primal_bound=INF, frontier_batch=None,
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
-                 propagate=None, reduced_cost=None, **kwargs):
+                 propagate=None, reduced_cost=None, objective_step=None, local_search=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -209,7 +209,20 @@ class BranchAndBound(BaseAlgorithm):
         of its integer columns tightened from its reduced costs and the incumbent's objective, one GPU workgroup
         per node (include/mipx_rcfix.h), in place before its children are written: the whole subtree inherits
         them.  The optimum is the same; the nodes evaluated on the way differ.  Every step is then finished on
-        the host.  Counters: `reduced_cost_stats`."""
+        the host.  Counters: `reduced_cost_stats`.
+        objective_step (extension; needs frontier_batch and gomory_cuts=False, not with comm, dual_function or
+        tree_record, so not with restart; default None = off): True or a positive float, the step by which the
+        objective values of integer-feasible points differ (True: the gcd of the costs of a pure-integer objective,
+        utils/objective_step.objective_step_of; a ValueError where that does not exist).  With an incumbent U
+        the search then closes every node whose bound is above U - step (include/mipx_objstep.h) instead of only
+        those at U or above, and counts such a node as a leaf of value U.  An initial_primal_bound must then be
+        the objective of a feasible point.  The optimum is the same; the nodes evaluated on the way are fewer
+        once an incumbent is known.  Every step is then finished on the host.  Counters: `objective_step_stats`.
+        local_search (extension; needs primal_heuristic; default None = off): True or a positive number of moves.
+        Every point the heuristic ends feasible on goes through a pair-move local search on the GPU right behind
+        it (include/mipx_lsearch.h): unit moves of one integer column or of two at once that lower the objective
+        and keep every row, the best first, at most that many per point (True: 64).  Inherited by restart()
+        with primal_heuristic.  Counters: `local_search_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -219,7 +232,8 @@ class BranchAndBound(BaseAlgorithm):
         # what restart() hands to the search it makes: the options as given, the node kwargs before any call
         self._given = dict(node_limit=node_limit, mip_gap=mip_gap, logging=logging, max_run_time=max_run_time,
                            frontier_batch=frontier_batch, pool_capacity=pool_capacity, anchor=anchor, dive=dive,
-                           host_spill=host_spill, tree_record=tree_record, primal_heuristic=primal_heuristic)
+                           host_spill=host_spill, tree_record=tree_record, primal_heuristic=primal_heuristic,
+                           local_search=local_search)
         self._given_kwargs = dict(kwargs)
         self.restart_stats = None
         self.lp_batch = lp_batch
@@ -296,6 +310,28 @@ class BranchAndBound(BaseAlgorithm):
             'would miss the tightened ones'
         self._reduced_cost = reduced_cost
         self.reduced_cost_stats = None
+        assert objective_step is None or objective_step is True or (
+            isinstance(objective_step, (int, float)) and not isinstance(objective_step, bool) and
+            0 < objective_step < INF), 'objective_step is None, True or a positive finite step'
+        assert objective_step is None or frontier_batch is not None, \
+            'objective_step needs frontier_batch (it is a cutoff of the native engine)'
+        assert objective_step is None or comm is None, 'objective_step cannot be combined with comm'
+        assert objective_step is None or kwargs.get('gomory_cuts', True) is False, \
+            'objective_step needs gomory_cuts=False: cut-round trees are finished another way'
+        assert objective_step is None or not dual_function, \
+            'objective_step cannot be combined with dual_function: a recorded bound would depend on the incumbent'
+        assert objective_step is None or not tree_record, \
+            'objective_step cannot be combined with tree_record (and so with restart): a recorded bound would ' \
+            'depend on the incumbent'
+        self._objective_step = objective_step
+        self.objective_step_stats = None
+        assert local_search is None or local_search is True or (
+            isinstance(local_search, int) and not isinstance(local_search, bool) and local_search > 0), \
+            'local_search is None, True or a positive number of moves per point'
+        assert local_search is None or primal_heuristic is not None, \
+            'local_search needs primal_heuristic (it runs on the points the heuristic ends feasible on)'
+        self._local_search = local_search
+        self.local_search_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -351,6 +387,9 @@ class BranchAndBound(BaseAlgorithm):
         self.mip_gap = mip_gap
         self.logging = logging
         self.max_run_time = max_run_time
+        if self._objective_step is True:   # (the gcd of the costs, or a ValueError that asks for the step)
+            from simple_mip_solver_amd.utils.objective_step import objective_step_of
+            self._objective_step = objective_step_of(self)
 
     @property
     def dual_bound(self):
@@ -472,6 +511,10 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_tree_record(True)
             if self._primal_heuristic:
                 self._native.set_heuristic(self._primal_heuristic)
+            if self._local_search:
+                self._native.set_local_search(self._local_search)
+            if self._objective_step:
+                self._native.set_objective_step(self._objective_step)
             if self._propagate:
                 self._native.set_propagation(self._propagate)
             if self._reduced_cost:
@@ -539,13 +582,18 @@ class BranchAndBound(BaseAlgorithm):
             self.propagation_stats = self._native.propagation_stats()
         if self._reduced_cost:
             self.reduced_cost_stats = self._native.reduced_cost_stats()
+        if self._objective_step:
+            self.objective_step_stats = self._native.objective_step_stats()
+        if self._local_search:
+            self.local_search_stats = self._native.local_search_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')
             for key, value in totals.items():
                 self._kwargs[key] = self._native_totals0.get(key, 0) + value
 
-    _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive', 'primal_heuristic')
+    _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive', 'primal_heuristic',
+                          'local_search')
 
     def restart(self, b, **overrides):
         """A new, unsolved BranchAndBound for the same A, c, bounds and integer indices at the right-hand side
@@ -555,8 +603,9 @@ class BranchAndBound(BaseAlgorithm):
         points of the root box at every b, so the restarted search is exact.  b follows the convention of
         find_parameterized_dual_bound (a CyLPArray of the constraint's shape, negated with the same warning if
         the constraints were flipped at instantiation).  Same Node class and keyword options; overrides may
-        change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor, dive and
-        primal_heuristic.
+        change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor, dive,
+        primal_heuristic and local_search (local_search runs on the heuristic's points: an override that turns
+        primal_heuristic off turns an inherited local_search off with it).
         Needs frontier_batch and tree_record=True and a solve() before; not with comm; the restarted search
         records no dual function.  `restart_stats` of the new search reports the seeding."""
         assert self.frontier_batch is not None and self._tree_record, \
@@ -573,6 +622,8 @@ class BranchAndBound(BaseAlgorithm):
             'the shape of the RHS being added should match that of each node'
         opts = dict(self._given)
         opts.update({k: v for k, v in overrides.items() if k != 'dual_function'})
+        if not opts.get('primal_heuristic') and 'local_search' not in overrides:
+            opts['local_search'] = None   # (the local search runs on the heuristic's points: it leaves with it)
         assert isinstance(opts['frontier_batch'], int) and 0 < opts['frontier_batch'] <= self.frontier_batch, \
             'a restarted search steps with at most the frontier_batch of its source'
         if self._swapped_constraint_direction:
@@ -609,6 +660,8 @@ class BranchAndBound(BaseAlgorithm):
             self._native.set_host_spill(self._host_spill)
         if self._primal_heuristic:
             self._native.set_heuristic(self._primal_heuristic)
+        if self._local_search:
+            self._native.set_local_search(self._local_search)
         self.restart_stats = self._native.restart_stats()
         self._kwargs['next_node_idx'] = source._kwargs['next_node_idx']
 

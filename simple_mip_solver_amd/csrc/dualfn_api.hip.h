@@ -19,6 +19,7 @@ int mipx_tree_set_dual_record(mipx_tree *t, int64_t max_bytes, int rows, const i
     if (t->cuts) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_dual_record: not with cut rounds");
     if (t->pg.on) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_dual_record: not with the bound propagation (mipx_tree_set_propagation)");
     if (t->rc.on) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_dual_record: not with the reduced-cost tightening (mipx_tree_set_reduced_cost)");
+    if (t->os.on) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_dual_record: not with the objective step (mipx_tree_set_objective_step)");
     if (rows < 0 || (t->m > 0 && (!pos || !sign)))
         return fail(ctx, MIPX_EINVAL, "mipx_tree_set_dual_record: bad row map");
     for (int e = 0; e < t->m; e++)

@@ -57,6 +57,8 @@ int mipx_tree_set_heuristic(mipx_tree *t, int points_per_step, int every_steps, 
         HIP_TRY(ctx, hipMemcpy(hr.d_lu, t->root_l.data(), n * 8, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(hr.d_lu + n, t->root_u.data(), n * 8, hipMemcpyHostToDevice));
     }
+    if (t->ls.on && P > t->ls.cap)
+        return fail(ctx, MIPX_EINVAL, "mipx_tree_set_heuristic: more points than the local search was set for (mipx_tree_set_local_search(t, 0) first)");
     if (P > hr.cap) {   // (set again with more points: the step buffers grow; nothing is in flight before the first step)
         for (int k = 0; k < 3; k++) {
             if (hr.d_x[k]) (void)hipFree(hr.d_x[k]);

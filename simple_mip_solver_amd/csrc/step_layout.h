@@ -88,6 +88,15 @@ struct HeurOut {
     template <class Base> View<Base> view(Base *b) const { return {at<double>(b, obj), at<int32_t>(b, status), at<int32_t>(b, moves)}; }
 };
 
+// Local search output behind the heuristic's, cap points: [status] (i32) [moves: singles, pairs per point] (i32).
+struct LsOut {
+    size_t status, moves, end;
+    explicit LsOut(size_t cap) : status(0), moves(4 * cap), end(12 * cap) {}
+    size_t bytes() const { return end; }
+    template <class Base> struct View { Like<int32_t, Base> *status, *moves; };
+    template <class Base> View<Base> view(Base *b) const { return {at<int32_t>(b, status), at<int32_t>(b, moves)}; }
+};
+
 // Bound propagation output, cap nodes: [status | changed | rounds | capped], i32 each.
 struct PropOut {
     size_t status, changed, rounds, capped, end;

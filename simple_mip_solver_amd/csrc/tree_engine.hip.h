@@ -24,6 +24,7 @@
 #include "treerec_kernels.hip.h"
 #include "restart_kernels.hip.h"
 #include "heur_kernels.hip.h"
+#include "lsearch_kernels.hip.h"
 #include "prop_kernels.hip.h"
 #include "rcfix_kernels.hip.h"
 #include "cglp_kernels.hip.h"
@@ -303,6 +304,7 @@ struct StepBuf {
     hipEvent_t df_e0 = nullptr, df_e1 = nullptr;
     bool df_timed = false;
     int heur_n = 0;   // primal heuristic: the points of this step it was launched on (0: none)
+    int ls_n = 0;     // local search: the points of this step it was launched on behind the heuristic (0: none)
     int prop_n = 0;   // bound propagation: the nodes of this step it was launched on (0: none)
     std::vector<int> rc_cnt;          // reduced-cost tightening: the parents it was launched on, per level, not yet
     hipStream_t rc_stream = nullptr;  // collected (empty: none), and the stream the launches went to
@@ -390,6 +392,25 @@ struct HeurState {
     hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
     int64_t tried = 0, feasible = 0, stuck = 0, capped = 0, repair = 0, lift = 0, installed = 0;
     double us = 0.0;                 // device time of heur_round_repair
+};
+
+// Pair-move local search behind the heuristic (include/mipx_lsearch.h): the move cap and, per step buffer, what
+// comes down with each step (step_layout::LsOut); the points and their objectives are the heuristic's, in place.
+struct LsState {
+    bool on = false;
+    int max_moves = 0;
+    int cap = 0;                     // points the step buffers are laid out for (the heuristic's cap)
+    int32_t *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    int64_t run = 0, improved = 0, singles = 0, pairs = 0, capped = 0, installed = 0;
+    double us = 0.0;                 // device time of ls_pair_search
+};
+
+// Objective step (include/mipx_objstep.h): the step and the counters.
+struct ObjStepState {
+    bool on = false;
+    double step = 0.0;
+    int64_t popped = 0, unbranched = 0, launches = 0;
 };
 
 // Bound propagation (include/mipx_prop.h): the option's parameters and, per step buffer, what comes down with
@@ -548,6 +569,8 @@ struct mipx_tree {
     TreeRec tr;
     RestartRec rs;
     HeurState hr;
+    LsState ls;
+    ObjStepState os;
     PropState pg;
     RcState rc;
     // cut migration (mipx_tree_set_cut_migration): the top cm_rows rows of the cut store take the cut rows
@@ -571,6 +594,16 @@ double tree_open_min(mipx_tree *t) {
     if (t->search == 0) return t->heap.empty() ? inf : t->heap.h[0].key;
     while (!t->open_bounds.empty() && !t->is_open[t->open_bounds.top().second]) t->open_bounds.pop();
     return t->open_bounds.empty() ? inf : t->open_bounds.top().first;
+}
+
+// What a node's bound is compared with to decide whether the node goes on, and what the kernels get as their
+// cutoff: the incumbent's value, or with an objective step (include/mipx_objstep.h) the value one step below it plus
+// a slack where that is lower.  +inf without an incumbent.
+double tree_cutoff(const mipx_tree *t) {
+    const double U = t->primal;
+    if (!t->os.on || !std::isfinite(U)) return U;
+    const double C = U - t->os.step + 1e-6 * std::fmax(1.0, std::fabs(U));
+    return C < U ? C : U;
 }
 
 double tree_dual_bound(mipx_tree *t) { return std::fmin(tree_open_min(t), t->closed_min); }   // (of this rank's shard)
@@ -650,7 +683,7 @@ int launch_lp(mipx_tree *t, int batch, const double *l, const double *u, const i
         a.dive = dive->dive; a.dive_off = batch; a.rule = t->rule; a.n_int = t->n_int;
         const TabPtr tb = tab_at(t, t->fast_ok ? t->tab_host : 0);
         a.int_idx = t->d_int_idx; a.cost_l = tb.cl; a.cost_r = tb.cr; a.has_entry = tb.has;
-        a.dive_cutoff = t->primal;
+        a.dive_cutoff = tree_cutoff(t);
         a.dive_var = dive->d.dvar; a.dive_dir = dive->d.ddir; a.dive_val = dive->d.dval;
         a.dive_preset = 1;           // the kernel itself marks "no child / no dive" first
         a.zero16 = dive->d.ask_count; // and zeroes K4's request counter
@@ -706,7 +739,26 @@ int heur_launch(const mipx_problem *p, hipStream_t st, int batch, const double *
     return MIPX_OK;
 }
 
-// The step's node LP solutions (level 0, the first positions) through the heuristic, behind its node LPs.
+// One launch of ls_pair_search over `batch` points in device memory, queued on `st` (d_gate: null, or per point the
+// status of the heuristic that made it -- a point whose entry is not 0 is skipped and left as it is; d_x_out may be d_x).
+int ls_launch(const mipx_problem *p, hipStream_t st, int batch, const double *d_x, const double *d_l, const double *d_u,
+              const int32_t *d_int_idx, int n_int, double tol, int max_moves, const uint8_t *d_skip, const int32_t *d_gate,
+              double *d_x_out, double *d_obj, int32_t *d_status, int32_t *d_moves) {
+    mipx_ctx *ctx = p->ctx;
+    if (p->m > mipx::kLsMax || p->n > mipx::kLsMax) return fail(ctx, MIPX_ETOOBIG, "local search: more than 1024 rows or columns");
+    if (batch <= 0) return MIPX_OK;
+    mipx::LsArgs a;
+    a.m = p->m; a.n = p->n; a.n_int = n_int; a.max_moves = max_moves; a.tol = tol;
+    a.A = p->dA; a.b = p->db; a.c = p->dc; a.l = d_l; a.u = d_u; a.int_idx = d_int_idx;
+    a.x = d_x; a.skip = d_skip; a.gate = d_gate;
+    a.x_out = d_x_out; a.obj_out = d_obj; a.status_out = d_status; a.moves_out = d_moves;
+    hipLaunchKernelGGL(mipx::ls_pair_search, dim3((unsigned)batch), dim3(mipx::kLsNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
+// The step's node LP solutions (level 0, the first positions) through the heuristic, behind its node LPs, and the
+// heuristic's feasible points through the local search right behind it, in place.
 int heur_step_launch(mipx_tree *t, StepBuf &S) {
     HeurState &hr = t->hr;
     S.heur_n = 0;
@@ -721,6 +773,17 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(hr.e1[bi], st));
     S.heur_n = P;
+    S.ls_n = 0;
+    LsState &ls = t->ls;
+    if (ls.on) {
+        const auto lo = step_layout::LsOut((size_t)ls.cap).view(ls.d_out[bi]);
+        HIP_TRY(ctx, hipEventRecord(ls.e0[bi], st));
+        const int lrc = ls_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, ls.max_moves,
+                                  nullptr, o.status, hr.d_x[bi], o.obj, lo.status, lo.moves);
+        if (lrc) return lrc;
+        HIP_TRY(ctx, hipEventRecord(ls.e1[bi], st));
+        S.ls_n = P;
+    }
     return MIPX_OK;
 }
 
@@ -737,6 +800,26 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
     if (hipEventElapsedTime(&ms, hr.e0[bi], hr.e1[bi]) == hipSuccess) hr.us += 1000.0 * ms;
     const auto o = lay.view((const char *)hr.h_out[bi]);
     const double *obj = o.obj; const int32_t *status = o.status, *moves = o.moves;
+    // local search: its counters; the objectives above are already the improved ones
+    LsState &ls = t->ls;
+    const int LP = S.ls_n;
+    S.ls_n = 0;
+    const int32_t *ls_moves = nullptr;
+    if (LP > 0) {
+        const step_layout::LsOut llay((size_t)ls.cap);
+        if ((rc = tree_d2h(t, ls.h_out[bi], ls.d_out[bi], llay.bytes()))) return rc;
+        if (hipEventElapsedTime(&ms, ls.e0[bi], ls.e1[bi]) == hipSuccess) ls.us += 1000.0 * ms;
+        const auto lo = llay.view((const int32_t *)ls.h_out[bi]);
+        ls_moves = lo.moves;
+        for (int k = 0; k < LP; k++) {
+            if (lo.status[k] == MIPX_LS_SKIPPED) continue;
+            ls.run++;
+            ls.singles += lo.moves[2 * k];
+            ls.pairs += lo.moves[2 * k + 1];
+            if (lo.moves[2 * k] + lo.moves[2 * k + 1] > 0) ls.improved++;
+            if (lo.status[k] == MIPX_LS_CAPPED) ls.capped++;
+        }
+    }
     int best = -1;
     for (int k = 0; k < P; k++) {
         if (status[k] == MIPX_HEUR_SKIPPED) continue;
@@ -757,6 +840,7 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         // dual bound of an emptied queue would end above the incumbent instead of on it)
         t->closed_min = std::fmin(t->closed_min, obj[best]);
         hr.installed++;
+        if (ls_moves && ls_moves[2 * best] + ls_moves[2 * best + 1] > 0) ls.installed++;
     }
     return MIPX_OK;
 }
@@ -788,7 +872,7 @@ int prop_step_launch(mipx_tree *t, StepBuf &S) {
     hipStream_t st = ctx->stream;
     const int bi = (int)(&S - t->buf), B = S.B;
     const auto o = step_layout::PropOut((size_t)pg.cap).view(pg.d_out[bi]);
-    const double cutoff = pg.use_cutoff ? t->primal : std::numeric_limits<double>::infinity();
+    const double cutoff = pg.use_cutoff ? tree_cutoff(t) : std::numeric_limits<double>::infinity();
     HIP_TRY(ctx, hipEventRecord(pg.e0[bi], st));
     const int rc = prop_launch(t->prob, st, B, S.d_slot, t->pool_l, t->pool_u, t->d_int_idx, t->n_int, cutoff, pg.tol,
                                pg.max_rounds, t->pool_l, t->pool_u, o.status, o.changed, o.rounds, o.capped);
@@ -903,7 +987,7 @@ int rc_level_launch(mipx_tree *t, StepBuf &S, hipStream_t cs, int level, int cou
     const size_t off = lay.level((size_t)level);
     HIP_TRY(ctx, hipEventRecord(rs.e0[bi][level], cs));
     const int rc = rc_launch(t->prob, cs, count, d.slot + off, d.pos + off, t->pool_l, t->pool_u, rs.d_y[bi], t->d_int_idx, t->n_int,
-                             t->primal, rs.tol, rs.dtol, t->pool_l, t->pool_u, nullptr, d.status + off, d.changed + off);
+                             tree_cutoff(t), rs.tol, rs.dtol, t->pool_l, t->pool_u, nullptr, d.status + off, d.changed + off);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(rs.e1[bi][level], cs));
     S.rc_cnt.push_back(count);
@@ -1263,13 +1347,17 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
     S.B = 0;
     S.in_flight = false;
     S.inflight_min = std::numeric_limits<double>::infinity();
+    const double cut = tree_cutoff(t);   // (the incumbent does not change while the batch is popped)
     auto take = [&](int64_t id) {
         if (t->search != 0) t->is_open[id] = 0;
         NodeRec &nd = t->nodes[id];
         const int32_t slot = nd.slot;
         nd.slot = -1;  // (the row itself is released when the step is finished)
-        if (!(nd.dual_bound < t->primal)) {
-            t->closed_min = std::fmin(t->closed_min, nd.dual_bound);
+        if (!(nd.dual_bound < cut)) {
+            // (closed only because of the objective step: nothing in it is below the incumbent, a leaf of that value)
+            const bool by_step = nd.dual_bound < t->primal;
+            if (by_step) t->os.popped++;
+            t->closed_min = std::fmin(t->closed_min, by_step ? t->primal : nd.dual_bound);
             if (t->tr.on) t->tr.closed(id);
             if (spilled(slot)) spill_release(t, slot);   // (its record is dropped, never reloaded)
             else t->free_slots.push_back(slot);
@@ -1296,6 +1384,7 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
     }
     const int B = (int)ids.size();
     if (B == 0) return MIPX_OK;
+    if (cut < t->primal) t->os.launches++;
     if (t->hs.on_host > 0) {   // (rows for the batch's spilled nodes: before the budget below)
         const int arc = spill_assign(t, S);
         if (arc) return arc;
@@ -1887,6 +1976,7 @@ int finish_table(mipx_tree *t, FinishWork &W) {
     // node by node; per node its probes (ascending integer index, left then right), then its own branch unless just initialised
     size_t e = 0;
     bool changed = false;
+    const double cut = tree_cutoff(t);
     for (int k : W.todo) {   // (the requests are sorted by node: the nodes with requests come in that order)
         if (!(status[k] == 0 || status[k] == 2)) continue;   // (not lp_feasible)
         const NodeRec &nd = S.recs[k];
@@ -1909,7 +1999,7 @@ int finish_table(mipx_tree *t, FinishWork &W) {
         // the dive child: the update for the branch that made it -- like any node only if its own LP is feasible
         // (pseudo_cost.py:42-43), and only where the evaluation will accept the dive (the reference never creates that
         // child under a pruned or integral parent); a plunge: level by level, each child under the node before it
-        for (int pos = k; W.dived(pos) && obj[pos] < t->primal && !h.mipf[pos] && (status[pos] == 0 || status[pos] == 2); pos += B) {
+        for (int pos = k; W.dived(pos) && obj[pos] < cut && !h.mipf[pos] && (status[pos] == 0 || status[pos] == 2); pos += B) {
             const int cp = pos + B;
             if (!(status[cp] == 0 || status[cp] == 2)) break;
             const double vc = h.ddir[pos] == 0 ? h.dval[pos] - std::floor(h.dval[pos]) : std::ceil(h.dval[pos]) - h.dval[pos];
@@ -1998,6 +2088,10 @@ int64_t evaluate_node(mipx_tree *t, FinishWork &W, int64_t id, int pos, int32_t 
         if (h.mipf[pos]) {
             t->primal = obj[pos];
             W.incumbent_pos = pos;
+        } else if (!(obj[pos] < tree_cutoff(t))) {
+            // (only with an objective step: the node holds nothing below the incumbent, a leaf of that value)
+            leaf_value = t->primal;
+            t->os.unbranched++;
         } else if (bvar >= 0) {
             if (t->free_slots.size() < 2) { err = fail(t->ctx, MIPX_ENOMEM, "tree: node pool exhausted"); return -1; }
             branched_on = bvar;
@@ -3074,6 +3168,15 @@ void mipx_tree_destroy(mipx_tree *t) {
         }
     }
     {
+        LsState &ls = t->ls;
+        for (int k = 0; k < 3; k++) {
+            if (ls.d_out[k]) (void)hipFree(ls.d_out[k]);
+            if (ls.h_out[k]) (void)hipHostFree(ls.h_out[k]);
+            if (ls.e0[k]) (void)hipEventDestroy(ls.e0[k]);
+            if (ls.e1[k]) (void)hipEventDestroy(ls.e1[k]);
+        }
+    }
+    {
         RcState &rs = t->rc;
         for (int k = 0; k < 3; k++) {
             if (rs.d_y[k]) (void)hipFree(rs.d_y[k]);
@@ -3522,6 +3625,7 @@ int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps) {
     if (c && t->hr.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the primal heuristic (mipx_tree_set_heuristic)");
     if (c && t->pg.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the bound propagation (mipx_tree_set_propagation)");
     if (c && t->rc.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the reduced-cost tightening (mipx_tree_set_reduced_cost)");
+    if (c && t->os.on) return fail(t->ctx, MIPX_EINVAL, "mipx_tree_set_comm: not with the objective step (mipx_tree_set_objective_step)");
     t->comm = c;
     t->x_every = c ? every_steps : 0;
     if (!c) return MIPX_OK;
@@ -3904,3 +4008,5 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "heur_api.hip.h"
 #include "prop_api.hip.h"
 #include "rcfix_api.hip.h"
+#include "lsearch_api.hip.h"
+#include "objstep_api.hip.h"

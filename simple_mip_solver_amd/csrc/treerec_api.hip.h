@@ -119,6 +119,7 @@ int mipx_tree_set_tree_record(mipx_tree *t, int on) {
     if (t->n > 65536) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_tree_record: more than 65536 columns");
     if (on && t->pg.on) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_tree_record: not with the bound propagation (mipx_tree_set_propagation)");
     if (on && t->rc.on) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_tree_record: not with the reduced-cost tightening (mipx_tree_set_reduced_cost)");
+    if (on && t->os.on) return fail(ctx, MIPX_EINVAL, "mipx_tree_set_tree_record: not with the objective step (mipx_tree_set_objective_step)");
     TreeRec &tr = t->tr;
     if (!on) {   // (before the first step nothing has been recorded; the finish mode stays as it is)
         tr.on = false;
