@@ -539,5 +539,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_rcfix.h"   /* reduced-cost bound tightening from the node LPs' row duals on the GPU */
 #include "mipx_lsearch.h" /* pair-move local search behind the primal heuristic on the GPU */
 #include "mipx_objstep.h" /* objective-step cutoff of the frontier engine */
+#include "mipx_fixprop.h" /* fix-and-propagate dive behind the primal heuristic on the GPU */
 
 #endif /* MIPX_H */

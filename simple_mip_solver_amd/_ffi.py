@@ -334,6 +334,20 @@ _OBJSTEP_SIGNATURES = {
 OBJSTEP_SYMBOLS = list(_OBJSTEP_SIGNATURES)
 OBJSTEP_STATS_KEYS = ('closed_at_pop', 'left_unbranched', 'launches') + tuple('reserved%d' % k for k in range(3, 8))
 
+# ... and those of include/mipx_fixprop.h (the fix-and-propagate dive behind the primal heuristic), which mipx.h
+# includes (tests/test_fix_propagate_abi.py checks them against that header)
+_FIXPROP_SIGNATURES = {
+    'mipx_fix_propagate_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _d, _d, _i, _i] + [_vp] * 5),
+    'mipx_tree_set_fix_propagate': (_i, [_vp, _i, _i]),
+    'mipx_tree_fix_propagate_stats': (_i, [_vp, _vp]),
+}
+FIXPROP_SYMBOLS = list(_FIXPROP_SIGNATURES)
+FIXPROP_STATS_KEYS = ('points', 'feasible', 'stuck', 'capped', 'fixings', 'tries', 'incumbents', 'kernel_us')
+FIXPROP_STATUS = {0: 'feasible', 1: 'stuck', 2: 'capped', 3: 'skipped', 4: 'infeasible_box', 5: 'rows'}
+# propagation calls per point that fix_propagate=True / set_fix_propagate(True) take at most, and the rounds of each
+DEFAULT_FIX_PROPAGATE_TRIES = 256
+DEFAULT_FIX_PROPAGATE_ROUNDS = 8
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -351,7 +365,8 @@ def lib():
                                       list(_TREEREC_SIGNATURES.items()) + list(_CGLP_SIGNATURES.items()) +
                                       list(_RESTART_SIGNATURES.items()) + list(_HEUR_SIGNATURES.items()) +
                                       list(_PROP_SIGNATURES.items()) + list(_RCFIX_SIGNATURES.items()) +
-                                      list(_LSEARCH_SIGNATURES.items()) + list(_OBJSTEP_SIGNATURES.items())):
+                                      list(_LSEARCH_SIGNATURES.items()) + list(_OBJSTEP_SIGNATURES.items()) +
+                                      list(_FIXPROP_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -834,6 +849,26 @@ class Problem:
         self.ctx.check(rc, 'mipx_pair_search_batch')
         return dict(x=xo, obj=obj, status=status, moves=moves)
 
+    def fix_propagate_batch(self, x, l, u, integer_indices, cutoff=None, tol=1e-9, max_rounds=DEFAULT_FIX_PROPAGATE_ROUNDS,
+                            max_tries=DEFAULT_FIX_PROPAGATE_TRIES, skip=None):
+        """The fix-and-propagate dive on host buffers (mipx_fix_propagate_batch, include/mipx_fixprop.h): x (batch, n)
+        points, l, u the bounds (n each), cutoff None or an objective value no point above which is of interest, skip an
+        optional (batch,) mask.  Returns dict of x (batch, n), obj, status (FIXPROP_STATUS codes) and counts (batch, 2:
+        fixings, tries)."""
+        n = self.n
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n)
+        B = x.shape[0]
+        l, u = _arr(l, np.float64, n), _arr(u, np.float64, n)
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        sk = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8).reshape(B)
+        cutoff = np.inf if cutoff is None else float(cutoff)
+        xo = np.zeros((B, n)); obj = np.zeros(B); status = np.zeros(B, np.int32); counts = np.zeros((B, 2), np.int32)
+        rc = lib().mipx_fix_propagate_batch(self._h, B, _ptr(x), _ptr(l), _ptr(u), _ptr(ii), len(ii), cutoff, float(tol),
+                                            int(max_rounds), int(max_tries), _ptr(sk), _ptr(xo), _ptr(obj), _ptr(status),
+                                            _ptr(counts))
+        self.ctx.check(rc, 'mipx_fix_propagate_batch')
+        return dict(x=xo, obj=obj, status=status, counts=counts)
+
     def propagate_batch(self, l, u, integer_indices, cutoff=None, tol=PROPAGATION_TOL, max_rounds=DEFAULT_PROPAGATION_ROUNDS):
         """Bound propagation on host buffers (mipx_propagate_batch, include/mipx_prop.h): l, u (batch, n) boxes,
         cutoff None or an objective value no point above which is of interest.  Returns dict of l, u (batch, n),
@@ -1272,6 +1307,19 @@ class Tree:
         out = np.zeros(8, np.int64)
         self.problem.ctx.check(lib().mipx_tree_local_search_stats(self._h, _ptr(out)), 'mipx_tree_local_search_stats')
         return dict(zip(LSEARCH_STATS_KEYS, (int(v) for v in out)))
+
+    def set_fix_propagate(self, max_tries=True, max_rounds=DEFAULT_FIX_PROPAGATE_ROUNDS):
+        """Run the fix-and-propagate dive behind the primal heuristic of every step, on the points its rounding did not
+        end feasible on (mipx_tree_set_fix_propagate, include/mipx_fixprop.h; True: DEFAULT_FIX_PROPAGATE_TRIES
+        propagation calls per point at most; 0 or False: off).  After set_heuristic."""
+        max_tries = DEFAULT_FIX_PROPAGATE_TRIES if max_tries is True else int(max_tries)
+        self.problem.ctx.check(lib().mipx_tree_set_fix_propagate(self._h, int(max_rounds), max_tries), 'mipx_tree_set_fix_propagate')
+
+    def fix_propagate_stats(self):
+        """dict(points, feasible, stuck, capped, fixings, tries, incumbents, kernel_us) (mipx_tree_fix_propagate_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_fix_propagate_stats(self._h, _ptr(out)), 'mipx_tree_fix_propagate_stats')
+        return dict(zip(FIXPROP_STATS_KEYS, (int(v) for v in out)))
 
     def set_objective_step(self, step):
         """Prune at one objective step below the incumbent (mipx_tree_set_objective_step, include/mipx_objstep.h):

@@ -125,7 +125,8 @@ class BranchAndBound(BaseAlgorithm):
                  logging=False, max_run_time=INF, initial_primal_bound=INF, frontier_batch=None,
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
-                 propagate=None, reduced_cost=None, objective_step=None, local_search=None, **kwargs):
+                 propagate=None, reduced_cost=None, objective_step=None, local_search=None, fix_propagate=None,
+                 **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -222,7 +223,15 @@ class BranchAndBound(BaseAlgorithm):
         Every point the heuristic ends feasible on goes through a pair-move local search on the GPU right behind
         it (include/mipx_lsearch.h): unit moves of one integer column or of two at once that lower the objective
         and keep every row, the best first, at most that many per point (True: 64).  Inherited by restart()
-        with primal_heuristic.  Counters: `local_search_stats`."""
+        with primal_heuristic.  Counters: `local_search_stats`.
+        fix_propagate (extension; needs primal_heuristic; default None = off): True or a positive number of tries.
+        Every point the heuristic's rounding does not end feasible on goes through a fix-and-propagate dive on the
+        GPU right behind it (include/mipx_fixprop.h): the integer columns are fixed one after the other, the most
+        integral first, each to the value nearest the LP point that the bound propagation over the rows (the
+        incumbent's objective as one more row) does not refuse, at most that many propagation calls per point
+        (True: 256).  A point the dive ends feasible is lifted by the heuristic, goes through local_search when
+        that is on, and competes for the step's incumbent.  Inherited by restart() with primal_heuristic.
+        Counters: `fix_propagate_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -233,7 +242,7 @@ class BranchAndBound(BaseAlgorithm):
         self._given = dict(node_limit=node_limit, mip_gap=mip_gap, logging=logging, max_run_time=max_run_time,
                            frontier_batch=frontier_batch, pool_capacity=pool_capacity, anchor=anchor, dive=dive,
                            host_spill=host_spill, tree_record=tree_record, primal_heuristic=primal_heuristic,
-                           local_search=local_search)
+                           local_search=local_search, fix_propagate=fix_propagate)
         self._given_kwargs = dict(kwargs)
         self.restart_stats = None
         self.lp_batch = lp_batch
@@ -332,6 +341,13 @@ class BranchAndBound(BaseAlgorithm):
             'local_search needs primal_heuristic (it runs on the points the heuristic ends feasible on)'
         self._local_search = local_search
         self.local_search_stats = None
+        assert fix_propagate is None or fix_propagate is True or (
+            isinstance(fix_propagate, int) and not isinstance(fix_propagate, bool) and fix_propagate > 0), \
+            'fix_propagate is None, True or a positive number of tries per point'
+        assert fix_propagate is None or primal_heuristic is not None, \
+            'fix_propagate needs primal_heuristic (it runs on the points the heuristic does not end feasible on)'
+        self._fix_propagate = fix_propagate
+        self.fix_propagate_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -513,6 +529,8 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_heuristic(self._primal_heuristic)
             if self._local_search:
                 self._native.set_local_search(self._local_search)
+            if self._fix_propagate:
+                self._native.set_fix_propagate(self._fix_propagate)
             if self._objective_step:
                 self._native.set_objective_step(self._objective_step)
             if self._propagate:
@@ -586,6 +604,8 @@ class BranchAndBound(BaseAlgorithm):
             self.objective_step_stats = self._native.objective_step_stats()
         if self._local_search:
             self.local_search_stats = self._native.local_search_stats()
+        if self._fix_propagate:
+            self.fix_propagate_stats = self._native.fix_propagate_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')
@@ -593,7 +613,7 @@ class BranchAndBound(BaseAlgorithm):
                 self._kwargs[key] = self._native_totals0.get(key, 0) + value
 
     _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive', 'primal_heuristic',
-                          'local_search')
+                          'local_search', 'fix_propagate')
 
     def restart(self, b, **overrides):
         """A new, unsolved BranchAndBound for the same A, c, bounds and integer indices at the right-hand side
@@ -604,8 +624,8 @@ class BranchAndBound(BaseAlgorithm):
         find_parameterized_dual_bound (a CyLPArray of the constraint's shape, negated with the same warning if
         the constraints were flipped at instantiation).  Same Node class and keyword options; overrides may
         change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor, dive,
-        primal_heuristic and local_search (local_search runs on the heuristic's points: an override that turns
-        primal_heuristic off turns an inherited local_search off with it).
+        primal_heuristic, local_search and fix_propagate (the last two run on the heuristic's points: an override
+        that turns primal_heuristic off turns an inherited local_search or fix_propagate off with it).
         Needs frontier_batch and tree_record=True and a solve() before; not with comm; the restarted search
         records no dual function.  `restart_stats` of the new search reports the seeding."""
         assert self.frontier_batch is not None and self._tree_record, \
@@ -624,6 +644,8 @@ class BranchAndBound(BaseAlgorithm):
         opts.update({k: v for k, v in overrides.items() if k != 'dual_function'})
         if not opts.get('primal_heuristic') and 'local_search' not in overrides:
             opts['local_search'] = None   # (the local search runs on the heuristic's points: it leaves with it)
+        if not opts.get('primal_heuristic') and 'fix_propagate' not in overrides:
+            opts['fix_propagate'] = None   # (and so does the dive)
         assert isinstance(opts['frontier_batch'], int) and 0 < opts['frontier_batch'] <= self.frontier_batch, \
             'a restarted search steps with at most the frontier_batch of its source'
         if self._swapped_constraint_direction:
@@ -662,6 +684,8 @@ class BranchAndBound(BaseAlgorithm):
             self._native.set_heuristic(self._primal_heuristic)
         if self._local_search:
             self._native.set_local_search(self._local_search)
+        if self._fix_propagate:
+            self._native.set_fix_propagate(self._fix_propagate)
         self.restart_stats = self._native.restart_stats()
         self._kwargs['next_node_idx'] = source._kwargs['next_node_idx']
 

@@ -25,6 +25,7 @@
 #include "restart_kernels.hip.h"
 #include "heur_kernels.hip.h"
 #include "lsearch_kernels.hip.h"
+#include "fixprop_kernels.hip.h"
 #include "prop_kernels.hip.h"
 #include "rcfix_kernels.hip.h"
 #include "cglp_kernels.hip.h"
@@ -305,6 +306,7 @@ struct StepBuf {
     bool df_timed = false;
     int heur_n = 0;   // primal heuristic: the points of this step it was launched on (0: none)
     int ls_n = 0;     // local search: the points of this step it was launched on behind the heuristic (0: none)
+    int fp_n = 0;     // fix-and-propagate dive: the points of this step it was launched on behind the heuristic (0: none)
     int prop_n = 0;   // bound propagation: the nodes of this step it was launched on (0: none)
     std::vector<int> rc_cnt;          // reduced-cost tightening: the parents it was launched on, per level, not yet
     hipStream_t rc_stream = nullptr;  // collected (empty: none), and the stream the launches went to
@@ -404,6 +406,18 @@ struct LsState {
     hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
     int64_t run = 0, improved = 0, singles = 0, pairs = 0, capped = 0, installed = 0;
     double us = 0.0;                 // device time of ls_pair_search
+};
+
+// Fix-and-propagate dive behind the heuristic (include/mipx_fixprop.h): the caps and, per step buffer, what comes
+// down with each step (step_layout::FpOut); the points are the heuristic's, in place.
+struct FpState {
+    bool on = false;
+    int max_rounds = 0, max_tries = 0;
+    int cap = 0;                     // points the step buffers are laid out for (the heuristic's cap)
+    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    int64_t tried = 0, feasible = 0, stuck = 0, capped = 0, fixings = 0, tries = 0, installed = 0;
+    double us = 0.0;                 // device time of fixprop_dive and of the lift behind it
 };
 
 // Objective step (include/mipx_objstep.h): the step and the counters.
@@ -570,6 +584,7 @@ struct mipx_tree {
     RestartRec rs;
     HeurState hr;
     LsState ls;
+    FpState fp;
     ObjStepState os;
     PropState pg;
     RcState rc;
@@ -757,8 +772,29 @@ int ls_launch(const mipx_problem *p, hipStream_t st, int batch, const double *d_
     return MIPX_OK;
 }
 
-// The step's node LP solutions (level 0, the first positions) through the heuristic, behind its node LPs, and the
-// heuristic's feasible points through the local search right behind it, in place.
+// One launch of fixprop_dive over `batch` points in device memory, queued on `st` (d_gate: null, or per point the
+// status of the heuristic that tried it first -- only its stuck and capped points are run, the others are left as
+// they are; d_x_out may be d_x).
+int fp_launch(const mipx_problem *p, hipStream_t st, int batch, const double *d_x, const double *d_l, const double *d_u,
+              const int32_t *d_int_idx, int n_int, double cutoff, double tol, int max_rounds, int max_tries, const uint8_t *d_skip,
+              const int32_t *d_gate, double *d_x_out, double *d_obj, int32_t *d_status, int32_t *d_counts) {
+    mipx_ctx *ctx = p->ctx;
+    if (p->m > mipx::kFpMax || p->n > mipx::kFpMax) return fail(ctx, MIPX_ETOOBIG, "fix-and-propagate dive: more than 1024 rows or columns");
+    if (batch <= 0) return MIPX_OK;
+    mipx::FixpropArgs a;
+    a.m = p->m; a.n = p->n; a.n_int = n_int; a.max_rounds = max_rounds; a.max_tries = max_tries;
+    a.cut = std::isfinite(cutoff) ? 1 : 0; a.tol = tol; a.cutoff = cutoff;
+    a.A = p->dA; a.b = p->db; a.c = p->dc; a.l = d_l; a.u = d_u; a.int_idx = d_int_idx;
+    a.x = d_x; a.skip = d_skip; a.gate = d_gate;
+    a.x_out = d_x_out; a.obj_out = d_obj; a.status_out = d_status; a.counts_out = d_counts;
+    hipLaunchKernelGGL(mipx::fixprop_dive, dim3((unsigned)batch), dim3(mipx::kFpNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
+// The step's node LP solutions (level 0, the first positions) through the heuristic, behind its node LPs; the points
+// it did not end feasible on through the fix-and-propagate dive, whose feasible points take their place and go through
+// the heuristic once more (the lift); and the feasible points of both through the local search, in place.
 int heur_step_launch(mipx_tree *t, StepBuf &S) {
     HeurState &hr = t->hr;
     S.heur_n = 0;
@@ -774,6 +810,22 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
     HIP_TRY(ctx, hipEventRecord(hr.e1[bi], st));
     S.heur_n = P;
     S.ls_n = 0;
+    S.fp_n = 0;
+    FpState &fp = t->fp;
+    const auto fo = step_layout::FpOut((size_t)(fp.on ? fp.cap : 0)).view(fp.on ? fp.d_out[bi] : nullptr);
+    if (fp.on) {
+        // the same LP points, gated by the heuristic's status; a dive point lands in the heuristic's slot of hr.d_x, its
+        // objective and the lifted one in the dive's own block (a point the lift skips has its objective there zeroed)
+        HIP_TRY(ctx, hipEventRecord(fp.e0[bi], st));
+        int frc = fp_launch(t->prob, st, P, S.d_x, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, tree_cutoff(t), hr.tol,
+                            fp.max_rounds, fp.max_tries, nullptr, o.status, hr.d_x[bi], fo.obj, fo.status, fo.counts);
+        if (frc) return frc;
+        frc = heur_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
+                          nullptr, fo.status, hr.d_x[bi], fo.obj, fo.lift_status, fo.lift_moves);
+        if (frc) return frc;
+        HIP_TRY(ctx, hipEventRecord(fp.e1[bi], st));
+        S.fp_n = P;
+    }
     LsState &ls = t->ls;
     if (ls.on) {
         const auto lo = step_layout::LsOut((size_t)ls.cap).view(ls.d_out[bi]);
@@ -781,6 +833,11 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
         const int lrc = ls_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, ls.max_moves,
                                   nullptr, o.status, hr.d_x[bi], o.obj, lo.status, lo.moves);
         if (lrc) return lrc;
+        if (fp.on) {   // ... and the lifted dive points, whose objectives and counts are in the dive's block
+            const int drc = ls_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
+                                      ls.max_moves, nullptr, fo.lift_status, hr.d_x[bi], fo.obj, fo.ls_status, fo.ls_moves);
+            if (drc) return drc;
+        }
         HIP_TRY(ctx, hipEventRecord(ls.e1[bi], st));
         S.ls_n = P;
     }
@@ -820,8 +877,48 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
             if (lo.status[k] == MIPX_LS_CAPPED) ls.capped++;
         }
     }
+    // fix-and-propagate dive: its counters, and which points are its own (their objectives are in its block)
+    FpState &fp = t->fp;
+    const int FP = S.fp_n;
+    S.fp_n = 0;
+    const double *fp_obj = nullptr;
+    const int32_t *fp_ok = nullptr, *fp_ls_moves = nullptr;
+    if (FP > 0) {
+        const step_layout::FpOut flay((size_t)fp.cap);
+        if ((rc = tree_d2h(t, fp.h_out[bi], fp.d_out[bi], flay.bytes()))) return rc;
+        if (hipEventElapsedTime(&ms, fp.e0[bi], fp.e1[bi]) == hipSuccess) fp.us += 1000.0 * ms;
+        const auto fo = flay.view((const char *)fp.h_out[bi]);
+        fp_obj = fo.obj;
+        fp_ok = fo.lift_status;   // (0: the dive ended feasible and the heuristic's second pass lifted the point)
+        for (int k = 0; k < FP; k++) {
+            if (fo.status[k] == MIPX_FP_SKIPPED) continue;
+            fp.tried++;
+            fp.fixings += fo.counts[2 * k];
+            fp.tries += fo.counts[2 * k + 1];
+            if (fo.status[k] == MIPX_FP_FEASIBLE) fp.feasible++;
+            if (fo.status[k] == MIPX_FP_STUCK) fp.stuck++;
+            if (fo.status[k] == MIPX_FP_CAPPED) fp.capped++;
+        }
+        if (LP > 0) {
+            fp_ls_moves = fo.ls_moves;
+            for (int k = 0; k < FP; k++) {
+                if (fo.ls_status[k] == MIPX_LS_SKIPPED) continue;
+                ls.run++;
+                ls.singles += fo.ls_moves[2 * k];
+                ls.pairs += fo.ls_moves[2 * k + 1];
+                if (fo.ls_moves[2 * k] + fo.ls_moves[2 * k + 1] > 0) ls.improved++;
+                if (fo.ls_status[k] == MIPX_LS_CAPPED) ls.capped++;
+            }
+        }
+    }
     int best = -1;
+    bool best_fp = false;
+    double best_obj = 0.0;
     for (int k = 0; k < P; k++) {
+        if (fp_ok && status[k] != MIPX_HEUR_SKIPPED && status[k] != MIPX_HEUR_FEASIBLE && fp_ok[k] == MIPX_HEUR_FEASIBLE &&
+            (best < 0 || fp_obj[k] < best_obj)) {
+            best = k; best_fp = true; best_obj = fp_obj[k];
+        }
         if (status[k] == MIPX_HEUR_SKIPPED) continue;
         hr.tried++;
         hr.repair += moves[2 * k];
@@ -830,17 +927,19 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         if (status[k] == MIPX_HEUR_CAPPED) hr.capped++;
         if (status[k] != MIPX_HEUR_FEASIBLE) continue;
         hr.feasible++;
-        if (best < 0 || obj[k] < obj[best]) best = k;
+        if (best < 0 || obj[k] < best_obj) { best = k; best_fp = false; best_obj = obj[k]; }
     }
-    if (best >= 0 && obj[best] < t->primal) {
-        t->primal = obj[best];
+    if (best >= 0 && best_obj < t->primal) {
+        t->primal = best_obj;
         if ((rc = tree_d2h(t, t->best_x.data(), hr.d_x[bi] + (size_t)best * n, (size_t)n * 8))) return rc;
         t->have_x = true;
         // (the point is a closed leaf of value obj: without it no closed leaf holds the incumbent's value, and the
         // dual bound of an emptied queue would end above the incumbent instead of on it)
-        t->closed_min = std::fmin(t->closed_min, obj[best]);
+        t->closed_min = std::fmin(t->closed_min, best_obj);
         hr.installed++;
-        if (ls_moves && ls_moves[2 * best] + ls_moves[2 * best + 1] > 0) ls.installed++;
+        if (best_fp) fp.installed++;
+        const int32_t *lm = best_fp ? fp_ls_moves : ls_moves;
+        if (lm && lm[2 * best] + lm[2 * best + 1] > 0) ls.installed++;
     }
     return MIPX_OK;
 }
@@ -3177,6 +3276,15 @@ void mipx_tree_destroy(mipx_tree *t) {
         }
     }
     {
+        FpState &fp = t->fp;
+        for (int k = 0; k < 3; k++) {
+            if (fp.d_out[k]) (void)hipFree(fp.d_out[k]);
+            if (fp.h_out[k]) (void)hipHostFree(fp.h_out[k]);
+            if (fp.e0[k]) (void)hipEventDestroy(fp.e0[k]);
+            if (fp.e1[k]) (void)hipEventDestroy(fp.e1[k]);
+        }
+    }
+    {
         RcState &rs = t->rc;
         for (int k = 0; k < 3; k++) {
             if (rs.d_y[k]) (void)hipFree(rs.d_y[k]);
@@ -4009,4 +4117,5 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "prop_api.hip.h"
 #include "rcfix_api.hip.h"
 #include "lsearch_api.hip.h"
+#include "fixprop_api.hip.h"
 #include "objstep_api.hip.h"
