@@ -83,6 +83,7 @@ int mipx_fix_propagate_batch(mipx_problem *p, int batch, const double *x, const 
  * MIPX_EINVAL: max_rounds < 1, max_tries < 0, a tree without the heuristic (mipx_tree_set_heuristic first, which
  * refuses cut rounds and a communicator), a tree that has stepped.  max_tries = 0 switches the dive off again.
  * A later mipx_tree_set_heuristic with more points than the dive was set for is refused, as with the local search.
+ * A tree that has the weighted row repair of mipx_wrepair.h on is refused as well (MIPX_EINVAL): one of the two.
  */
 int mipx_tree_set_fix_propagate(mipx_tree *t, int max_rounds, int max_tries);
 /*

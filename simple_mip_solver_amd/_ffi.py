@@ -348,6 +348,19 @@ FIXPROP_STATUS = {0: 'feasible', 1: 'stuck', 2: 'capped', 3: 'skipped', 4: 'infe
 DEFAULT_FIX_PROPAGATE_TRIES = 256
 DEFAULT_FIX_PROPAGATE_ROUNDS = 8
 
+# ... and those of include/mipx_wrepair.h (the weighted row repair behind the primal heuristic), which mipx.h includes
+# (tests/test_weighted_repair_abi.py checks them against that header)
+_WREPAIR_SIGNATURES = {
+    'mipx_weighted_repair_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _d, _i] + [_vp] * 6),
+    'mipx_tree_set_weighted_repair': (_i, [_vp, _i]),
+    'mipx_tree_weighted_repair_stats': (_i, [_vp, _vp]),
+}
+WREPAIR_SYMBOLS = list(_WREPAIR_SIGNATURES)
+WREPAIR_STATS_KEYS = ('points', 'feasible', 'capped', 'moves', 'bumps', 'incumbents', 'reserved6', 'kernel_us')
+WREPAIR_STATUS = {0: 'feasible', 2: 'capped', 3: 'skipped'}
+# moves and bumps per point that weighted_repair=True / set_weighted_repair(True) take at most
+DEFAULT_WEIGHTED_REPAIR_STEPS = 256
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -366,7 +379,7 @@ def lib():
                                       list(_RESTART_SIGNATURES.items()) + list(_HEUR_SIGNATURES.items()) +
                                       list(_PROP_SIGNATURES.items()) + list(_RCFIX_SIGNATURES.items()) +
                                       list(_LSEARCH_SIGNATURES.items()) + list(_OBJSTEP_SIGNATURES.items()) +
-                                      list(_FIXPROP_SIGNATURES.items())):
+                                      list(_FIXPROP_SIGNATURES.items()) + list(_WREPAIR_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -869,6 +882,25 @@ class Problem:
         self.ctx.check(rc, 'mipx_fix_propagate_batch')
         return dict(x=xo, obj=obj, status=status, counts=counts)
 
+    def weighted_repair_batch(self, x, l, u, integer_indices, tol=1e-9, max_steps=DEFAULT_WEIGHTED_REPAIR_STEPS, skip=None,
+                              gate=None):
+        """The weighted row repair on host buffers (mipx_weighted_repair_batch, include/mipx_wrepair.h): x (batch, n)
+        points, l, u the bounds (n each), skip an optional (batch,) mask, gate optional (batch,) statuses of the rounding
+        heuristic (only its stuck and capped points are run).  Returns dict of x (batch, n), obj, status (WREPAIR_STATUS
+        codes) and counts (batch, 2: moves, bumps)."""
+        n = self.n
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n)
+        B = x.shape[0]
+        l, u = _arr(l, np.float64, n), _arr(u, np.float64, n)
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        sk = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8).reshape(B)
+        gt = None if gate is None else np.ascontiguousarray(gate, dtype=np.int32).reshape(B)
+        xo = np.zeros((B, n)); obj = np.zeros(B); status = np.zeros(B, np.int32); counts = np.zeros((B, 2), np.int32)
+        rc = lib().mipx_weighted_repair_batch(self._h, B, _ptr(x), _ptr(l), _ptr(u), _ptr(ii), len(ii), float(tol), int(max_steps),
+                                              _ptr(sk), _ptr(gt), _ptr(xo), _ptr(obj), _ptr(status), _ptr(counts))
+        self.ctx.check(rc, 'mipx_weighted_repair_batch')
+        return dict(x=xo, obj=obj, status=status, counts=counts)
+
     def propagate_batch(self, l, u, integer_indices, cutoff=None, tol=PROPAGATION_TOL, max_rounds=DEFAULT_PROPAGATION_ROUNDS):
         """Bound propagation on host buffers (mipx_propagate_batch, include/mipx_prop.h): l, u (batch, n) boxes,
         cutoff None or an objective value no point above which is of interest.  Returns dict of l, u (batch, n),
@@ -1320,6 +1352,19 @@ class Tree:
         out = np.zeros(8, np.int64)
         self.problem.ctx.check(lib().mipx_tree_fix_propagate_stats(self._h, _ptr(out)), 'mipx_tree_fix_propagate_stats')
         return dict(zip(FIXPROP_STATS_KEYS, (int(v) for v in out)))
+
+    def set_weighted_repair(self, max_steps=True):
+        """Run the weighted row repair behind the primal heuristic of every step, on the points its rounding did not end
+        feasible on (mipx_tree_set_weighted_repair, include/mipx_wrepair.h; True: DEFAULT_WEIGHTED_REPAIR_STEPS moves
+        and bumps per point at most; 0 or False: off).  After set_heuristic; not together with set_fix_propagate."""
+        max_steps = DEFAULT_WEIGHTED_REPAIR_STEPS if max_steps is True else int(max_steps)
+        self.problem.ctx.check(lib().mipx_tree_set_weighted_repair(self._h, max_steps), 'mipx_tree_set_weighted_repair')
+
+    def weighted_repair_stats(self):
+        """dict(points, feasible, capped, moves, bumps, incumbents, reserved6, kernel_us) (mipx_tree_weighted_repair_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_weighted_repair_stats(self._h, _ptr(out)), 'mipx_tree_weighted_repair_stats')
+        return dict(zip(WREPAIR_STATS_KEYS, (int(v) for v in out)))
 
     def set_objective_step(self, step):
         """Prune at one objective step below the incumbent (mipx_tree_set_objective_step, include/mipx_objstep.h):

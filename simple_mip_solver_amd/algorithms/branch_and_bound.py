@@ -126,7 +126,7 @@ class BranchAndBound(BaseAlgorithm):
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
                  propagate=None, reduced_cost=None, objective_step=None, local_search=None, fix_propagate=None,
-                 **kwargs):
+                 weighted_repair=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -231,7 +231,14 @@ class BranchAndBound(BaseAlgorithm):
         incumbent's objective as one more row) does not refuse, at most that many propagation calls per point
         (True: 256).  A point the dive ends feasible is lifted by the heuristic, goes through local_search when
         that is on, and competes for the step's incumbent.  Inherited by restart() with primal_heuristic.
-        Counters: `fix_propagate_stats`."""
+        Counters: `fix_propagate_stats`.
+        weighted_repair (extension; needs primal_heuristic; not with fix_propagate; default None = off): True or a
+        positive number of steps.  Every point the heuristic's rounding does not end feasible on goes through a
+        weighted row repair on the GPU right behind it (include/mipx_wrepair.h): the heuristic's own unit moves, but
+        every row carries a weight, and where no move lowers the weighted violation the weights of the violated rows
+        go up by one, at most that many moves and bumps per point (True: 256).  A point it ends feasible is lifted
+        by the heuristic, goes through local_search when that is on, and competes for the step's incumbent.
+        Inherited by restart() with primal_heuristic.  Counters: `weighted_repair_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -242,7 +249,7 @@ class BranchAndBound(BaseAlgorithm):
         self._given = dict(node_limit=node_limit, mip_gap=mip_gap, logging=logging, max_run_time=max_run_time,
                            frontier_batch=frontier_batch, pool_capacity=pool_capacity, anchor=anchor, dive=dive,
                            host_spill=host_spill, tree_record=tree_record, primal_heuristic=primal_heuristic,
-                           local_search=local_search, fix_propagate=fix_propagate)
+                           local_search=local_search, fix_propagate=fix_propagate, weighted_repair=weighted_repair)
         self._given_kwargs = dict(kwargs)
         self.restart_stats = None
         self.lp_batch = lp_batch
@@ -348,6 +355,16 @@ class BranchAndBound(BaseAlgorithm):
             'fix_propagate needs primal_heuristic (it runs on the points the heuristic does not end feasible on)'
         self._fix_propagate = fix_propagate
         self.fix_propagate_stats = None
+        assert weighted_repair is None or weighted_repair is True or (
+            isinstance(weighted_repair, int) and not isinstance(weighted_repair, bool) and weighted_repair > 0), \
+            'weighted_repair is None, True or a positive number of steps per point'
+        assert weighted_repair is None or primal_heuristic is not None, \
+            'weighted_repair needs primal_heuristic (it runs on the points the heuristic does not end feasible on)'
+        assert weighted_repair is None or fix_propagate is None, \
+            'weighted_repair cannot be combined with fix_propagate (both take the points the heuristic does not end ' \
+            'feasible on, and running one behind the other is not built: choose one)'
+        self._weighted_repair = weighted_repair
+        self.weighted_repair_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -531,6 +548,8 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_local_search(self._local_search)
             if self._fix_propagate:
                 self._native.set_fix_propagate(self._fix_propagate)
+            if self._weighted_repair:
+                self._native.set_weighted_repair(self._weighted_repair)
             if self._objective_step:
                 self._native.set_objective_step(self._objective_step)
             if self._propagate:
@@ -606,6 +625,8 @@ class BranchAndBound(BaseAlgorithm):
             self.local_search_stats = self._native.local_search_stats()
         if self._fix_propagate:
             self.fix_propagate_stats = self._native.fix_propagate_stats()
+        if self._weighted_repair:
+            self.weighted_repair_stats = self._native.weighted_repair_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')
@@ -613,7 +634,7 @@ class BranchAndBound(BaseAlgorithm):
                 self._kwargs[key] = self._native_totals0.get(key, 0) + value
 
     _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive', 'primal_heuristic',
-                          'local_search', 'fix_propagate')
+                          'local_search', 'fix_propagate', 'weighted_repair')
 
     def restart(self, b, **overrides):
         """A new, unsolved BranchAndBound for the same A, c, bounds and integer indices at the right-hand side
@@ -624,8 +645,8 @@ class BranchAndBound(BaseAlgorithm):
         find_parameterized_dual_bound (a CyLPArray of the constraint's shape, negated with the same warning if
         the constraints were flipped at instantiation).  Same Node class and keyword options; overrides may
         change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor, dive,
-        primal_heuristic, local_search and fix_propagate (the last two run on the heuristic's points: an override
-        that turns primal_heuristic off turns an inherited local_search or fix_propagate off with it).
+        primal_heuristic, local_search, fix_propagate and weighted_repair (the last three run on the heuristic's
+        points: an override that turns primal_heuristic off turns the inherited ones off with it).
         Needs frontier_batch and tree_record=True and a solve() before; not with comm; the restarted search
         records no dual function.  `restart_stats` of the new search reports the seeding."""
         assert self.frontier_batch is not None and self._tree_record, \
@@ -646,6 +667,8 @@ class BranchAndBound(BaseAlgorithm):
             opts['local_search'] = None   # (the local search runs on the heuristic's points: it leaves with it)
         if not opts.get('primal_heuristic') and 'fix_propagate' not in overrides:
             opts['fix_propagate'] = None   # (and so does the dive)
+        if not opts.get('primal_heuristic') and 'weighted_repair' not in overrides:
+            opts['weighted_repair'] = None   # (and the weighted repair)
         assert isinstance(opts['frontier_batch'], int) and 0 < opts['frontier_batch'] <= self.frontier_batch, \
             'a restarted search steps with at most the frontier_batch of its source'
         if self._swapped_constraint_direction:
@@ -686,6 +709,8 @@ class BranchAndBound(BaseAlgorithm):
             self._native.set_local_search(self._local_search)
         if self._fix_propagate:
             self._native.set_fix_propagate(self._fix_propagate)
+        if self._weighted_repair:
+            self._native.set_weighted_repair(self._weighted_repair)
         self.restart_stats = self._native.restart_stats()
         self._kwargs['next_node_idx'] = source._kwargs['next_node_idx']
 

@@ -58,6 +58,8 @@ int mipx_tree_set_fix_propagate(mipx_tree *t, int max_rounds, int max_tries) {
         fp.on = false;
         return MIPX_OK;
     }
+    if (t->wr.on)
+        return fail(ctx, MIPX_EINVAL, "mipx_tree_set_fix_propagate: not with the weighted row repair (mipx_tree_set_weighted_repair(t, 0) first)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (t->hr.cap > fp.cap) {   // (the heuristic's step buffers grew or are new: nothing is in flight before the first step)
         const size_t out_bytes = step_layout::FpOut((size_t)t->hr.cap).bytes();

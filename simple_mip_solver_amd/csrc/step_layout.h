@@ -117,6 +117,26 @@ struct FpOut {
     }
 };
 
+// Weighted row repair output behind the heuristic's, cap points: [obj] (f64: the repaired point's, then the lifted
+// one) [status] (i32) [counts: moves, bumps per point] (i32), what the heuristic's second pass over the feasible ones
+// gives [lift_status | lift_moves: repair, lift per point] (i32), and what the local search gives on those
+// [ls_status | ls_moves: singles, pairs per point] (i32).
+struct WrOut {
+    size_t obj, status, counts, lift_status, lift_moves, ls_status, ls_moves, end;
+    explicit WrOut(size_t cap)
+        : obj(0), status(8 * cap), counts(status + 4 * cap), lift_status(counts + 8 * cap), lift_moves(lift_status + 4 * cap),
+          ls_status(lift_moves + 8 * cap), ls_moves(ls_status + 4 * cap), end(ls_moves + 8 * cap) {}
+    size_t bytes() const { return end; }
+    template <class Base> struct View {
+        Like<double, Base> *obj;
+        Like<int32_t, Base> *status, *counts, *lift_status, *lift_moves, *ls_status, *ls_moves;
+    };
+    template <class Base> View<Base> view(Base *b) const {
+        return {at<double>(b, obj), at<int32_t>(b, status), at<int32_t>(b, counts), at<int32_t>(b, lift_status),
+                at<int32_t>(b, lift_moves), at<int32_t>(b, ls_status), at<int32_t>(b, ls_moves)};
+    }
+};
+
 // Bound propagation output, cap nodes: [status | changed | rounds | capped], i32 each.
 struct PropOut {
     size_t status, changed, rounds, capped, end;

@@ -26,6 +26,7 @@
 #include "heur_kernels.hip.h"
 #include "lsearch_kernels.hip.h"
 #include "fixprop_kernels.hip.h"
+#include "wrepair_kernels.hip.h"
 #include "prop_kernels.hip.h"
 #include "rcfix_kernels.hip.h"
 #include "cglp_kernels.hip.h"
@@ -307,6 +308,7 @@ struct StepBuf {
     int heur_n = 0;   // primal heuristic: the points of this step it was launched on (0: none)
     int ls_n = 0;     // local search: the points of this step it was launched on behind the heuristic (0: none)
     int fp_n = 0;     // fix-and-propagate dive: the points of this step it was launched on behind the heuristic (0: none)
+    int wr_n = 0;     // weighted row repair: the points of this step it was launched on behind the heuristic (0: none)
     int prop_n = 0;   // bound propagation: the nodes of this step it was launched on (0: none)
     std::vector<int> rc_cnt;          // reduced-cost tightening: the parents it was launched on, per level, not yet
     hipStream_t rc_stream = nullptr;  // collected (empty: none), and the stream the launches went to
@@ -418,6 +420,18 @@ struct FpState {
     hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
     int64_t tried = 0, feasible = 0, stuck = 0, capped = 0, fixings = 0, tries = 0, installed = 0;
     double us = 0.0;                 // device time of fixprop_dive and of the lift behind it
+};
+
+// Weighted row repair behind the heuristic (include/mipx_wrepair.h): the cap and, per step buffer, what comes down
+// with each step (step_layout::WrOut); the points are the heuristic's, in place.  Never on together with the dive.
+struct WrState {
+    bool on = false;
+    int max_steps = 0;
+    int cap = 0;                     // points the step buffers are laid out for (the heuristic's cap)
+    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    int64_t tried = 0, feasible = 0, capped = 0, moves = 0, bumps = 0, installed = 0;
+    double us = 0.0;                 // device time of wrepair_steps and of the lift behind it
 };
 
 // Objective step (include/mipx_objstep.h): the step and the counters.
@@ -585,6 +599,7 @@ struct mipx_tree {
     HeurState hr;
     LsState ls;
     FpState fp;
+    WrState wr;
     ObjStepState os;
     PropState pg;
     RcState rc;
@@ -792,9 +807,29 @@ int fp_launch(const mipx_problem *p, hipStream_t st, int batch, const double *d_
     return MIPX_OK;
 }
 
+// One launch of wrepair_steps over `batch` points in device memory, queued on `st` (d_gate: null, or per point the
+// status of the heuristic that tried it first -- only its stuck and capped points are run; keep_gated: d_x_out holds
+// that heuristic's points, and the others are left as they are).
+int wr_launch(const mipx_problem *p, hipStream_t st, int batch, const double *d_x, const double *d_l, const double *d_u,
+              const int32_t *d_int_idx, int n_int, double tol, int max_steps, const uint8_t *d_skip, const int32_t *d_gate,
+              bool keep_gated, double *d_x_out, double *d_obj, int32_t *d_status, int32_t *d_counts) {
+    mipx_ctx *ctx = p->ctx;
+    if (p->m > mipx::kWrMax || p->n > mipx::kWrMax) return fail(ctx, MIPX_ETOOBIG, "weighted row repair: more than 1024 rows or columns");
+    if (batch <= 0) return MIPX_OK;
+    mipx::WrepairArgs a;
+    a.m = p->m; a.n = p->n; a.n_int = n_int; a.max_steps = max_steps; a.keep_gated = keep_gated ? 1 : 0; a.tol = tol;
+    a.A = p->dA; a.b = p->db; a.c = p->dc; a.l = d_l; a.u = d_u; a.int_idx = d_int_idx;
+    a.x = d_x; a.skip = d_skip; a.gate = d_gate;
+    a.x_out = d_x_out; a.obj_out = d_obj; a.status_out = d_status; a.counts_out = d_counts;
+    hipLaunchKernelGGL(mipx::wrepair_steps, dim3((unsigned)batch), dim3(mipx::kWrNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
 // The step's node LP solutions (level 0, the first positions) through the heuristic, behind its node LPs; the points
 // it did not end feasible on through the fix-and-propagate dive, whose feasible points take their place and go through
-// the heuristic once more (the lift); and the feasible points of both through the local search, in place.
+// the heuristic once more (the lift), or through the weighted row repair in the same way (one of the two at most); and
+// the feasible points of both through the local search, in place.
 int heur_step_launch(mipx_tree *t, StepBuf &S) {
     HeurState &hr = t->hr;
     S.heur_n = 0;
@@ -826,6 +861,22 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
         HIP_TRY(ctx, hipEventRecord(fp.e1[bi], st));
         S.fp_n = P;
     }
+    S.wr_n = 0;
+    WrState &wr = t->wr;
+    const auto wo = step_layout::WrOut((size_t)(wr.on ? wr.cap : 0)).view(wr.on ? wr.d_out[bi] : nullptr);
+    if (wr.on) {
+        // the dive's place, to the letter: the same LP points, gated by the heuristic's status; a repaired point lands in
+        // the heuristic's slot of hr.d_x, its objective and the lifted one in this option's own block
+        HIP_TRY(ctx, hipEventRecord(wr.e0[bi], st));
+        int wrc = wr_launch(t->prob, st, P, S.d_x, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, wr.max_steps,
+                            nullptr, o.status, true, hr.d_x[bi], wo.obj, wo.status, wo.counts);
+        if (wrc) return wrc;
+        wrc = heur_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
+                          nullptr, wo.status, hr.d_x[bi], wo.obj, wo.lift_status, wo.lift_moves);
+        if (wrc) return wrc;
+        HIP_TRY(ctx, hipEventRecord(wr.e1[bi], st));
+        S.wr_n = P;
+    }
     LsState &ls = t->ls;
     if (ls.on) {
         const auto lo = step_layout::LsOut((size_t)ls.cap).view(ls.d_out[bi]);
@@ -837,6 +888,11 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
             const int drc = ls_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
                                       ls.max_moves, nullptr, fo.lift_status, hr.d_x[bi], fo.obj, fo.ls_status, fo.ls_moves);
             if (drc) return drc;
+        }
+        if (wr.on) {   // ... or the lifted points of the weighted repair, in its block
+            const int wrc = ls_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
+                                      ls.max_moves, nullptr, wo.lift_status, hr.d_x[bi], wo.obj, wo.ls_status, wo.ls_moves);
+            if (wrc) return wrc;
         }
         HIP_TRY(ctx, hipEventRecord(ls.e1[bi], st));
         S.ls_n = P;
@@ -911,6 +967,37 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
             }
         }
     }
+    // weighted row repair: the same in its block (it is never on together with the dive, so fp_* are free for it)
+    WrState &wr = t->wr;
+    const int WP = S.wr_n;
+    S.wr_n = 0;
+    if (WP > 0) {
+        const step_layout::WrOut wlay((size_t)wr.cap);
+        if ((rc = tree_d2h(t, wr.h_out[bi], wr.d_out[bi], wlay.bytes()))) return rc;
+        if (hipEventElapsedTime(&ms, wr.e0[bi], wr.e1[bi]) == hipSuccess) wr.us += 1000.0 * ms;
+        const auto wo = wlay.view((const char *)wr.h_out[bi]);
+        fp_obj = wo.obj;
+        fp_ok = wo.lift_status;   // (0: the repair ended feasible and the heuristic's second pass lifted the point)
+        for (int k = 0; k < WP; k++) {
+            if (wo.status[k] == MIPX_WR_SKIPPED) continue;
+            wr.tried++;
+            wr.moves += wo.counts[2 * k];
+            wr.bumps += wo.counts[2 * k + 1];
+            if (wo.status[k] == MIPX_WR_FEASIBLE) wr.feasible++;
+            if (wo.status[k] == MIPX_WR_CAPPED) wr.capped++;
+        }
+        if (LP > 0) {
+            fp_ls_moves = wo.ls_moves;
+            for (int k = 0; k < WP; k++) {
+                if (wo.ls_status[k] == MIPX_LS_SKIPPED) continue;
+                ls.run++;
+                ls.singles += wo.ls_moves[2 * k];
+                ls.pairs += wo.ls_moves[2 * k + 1];
+                if (wo.ls_moves[2 * k] + wo.ls_moves[2 * k + 1] > 0) ls.improved++;
+                if (wo.ls_status[k] == MIPX_LS_CAPPED) ls.capped++;
+            }
+        }
+    }
     int best = -1;
     bool best_fp = false;
     double best_obj = 0.0;
@@ -937,7 +1024,7 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         // dual bound of an emptied queue would end above the incumbent instead of on it)
         t->closed_min = std::fmin(t->closed_min, best_obj);
         hr.installed++;
-        if (best_fp) fp.installed++;
+        if (best_fp) (WP > 0 ? wr.installed : fp.installed)++;
         const int32_t *lm = best_fp ? fp_ls_moves : ls_moves;
         if (lm && lm[2 * best] + lm[2 * best + 1] > 0) ls.installed++;
     }
@@ -3285,6 +3372,15 @@ void mipx_tree_destroy(mipx_tree *t) {
         }
     }
     {
+        WrState &wr = t->wr;
+        for (int k = 0; k < 3; k++) {
+            if (wr.d_out[k]) (void)hipFree(wr.d_out[k]);
+            if (wr.h_out[k]) (void)hipHostFree(wr.h_out[k]);
+            if (wr.e0[k]) (void)hipEventDestroy(wr.e0[k]);
+            if (wr.e1[k]) (void)hipEventDestroy(wr.e1[k]);
+        }
+    }
+    {
         RcState &rs = t->rc;
         for (int k = 0; k < 3; k++) {
             if (rs.d_y[k]) (void)hipFree(rs.d_y[k]);
@@ -4118,4 +4214,5 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "rcfix_api.hip.h"
 #include "lsearch_api.hip.h"
 #include "fixprop_api.hip.h"
+#include "wrepair_api.hip.h"
 #include "objstep_api.hip.h"
