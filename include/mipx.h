@@ -541,5 +541,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_objstep.h" /* objective-step cutoff of the frontier engine */
 #include "mipx_fixprop.h" /* fix-and-propagate dive behind the primal heuristic on the GPU */
 #include "mipx_wrepair.h" /* weighted row repair behind the primal heuristic on the GPU */
+#include "mipx_cube.h" /* cube search beside the primal heuristic on the GPU */
 
 #endif /* MIPX_H */

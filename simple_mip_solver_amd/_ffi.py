@@ -361,6 +361,20 @@ WREPAIR_STATUS = {0: 'feasible', 2: 'capped', 3: 'skipped'}
 # moves and bumps per point that weighted_repair=True / set_weighted_repair(True) take at most
 DEFAULT_WEIGHTED_REPAIR_STEPS = 256
 
+# ... and those of include/mipx_cube.h (the cube search beside the primal heuristic), which mipx.h includes
+# (tests/test_cube_search_abi.py checks them against that header)
+_CUBE_SIGNATURES = {
+    'mipx_cube_search_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _d, _d, _d, _i] + [_vp] * 5),
+    'mipx_tree_set_cube_search': (_i, [_vp, _i]),
+    'mipx_tree_cube_search_stats': (_i, [_vp, _vp]),
+}
+CUBE_SYMBOLS = list(_CUBE_SIGNATURES)
+CUBE_STATS_KEYS = ('points', 'found', 'none', 'columns', 'at_cap', 'incumbents', 'reserved6', 'kernel_us')
+CUBE_STATUS = {0: 'found', 1: 'none', 3: 'skipped'}
+# columns that cube_search=True / set_cube_search(True) enumerate at most, and the most that can be asked for
+DEFAULT_CUBE_SEARCH_COLUMNS = 16
+MAX_CUBE_SEARCH_COLUMNS = 20
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -379,7 +393,8 @@ def lib():
                                       list(_RESTART_SIGNATURES.items()) + list(_HEUR_SIGNATURES.items()) +
                                       list(_PROP_SIGNATURES.items()) + list(_RCFIX_SIGNATURES.items()) +
                                       list(_LSEARCH_SIGNATURES.items()) + list(_OBJSTEP_SIGNATURES.items()) +
-                                      list(_FIXPROP_SIGNATURES.items()) + list(_WREPAIR_SIGNATURES.items())):
+                                      list(_FIXPROP_SIGNATURES.items()) + list(_WREPAIR_SIGNATURES.items()) +
+                                      list(_CUBE_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -901,6 +916,24 @@ class Problem:
         self.ctx.check(rc, 'mipx_weighted_repair_batch')
         return dict(x=xo, obj=obj, status=status, counts=counts)
 
+    def cube_search_batch(self, x, l, u, integer_indices, cutoff=np.inf, tol=1e-9, ftol=1e-4,
+                          max_columns=DEFAULT_CUBE_SEARCH_COLUMNS, skip=None):
+        """The cube search on host buffers (mipx_cube_search_batch, include/mipx_cube.h): x (batch, n) points, l, u the
+        bounds (n each), cutoff an objective value only points below which are of interest, ftol the distance from an
+        integer above which a column counts as fractional, skip an optional (batch,) mask.  Returns dict of x
+        (batch, n), obj, status (CUBE_STATUS codes) and counts (batch, 2: k, code)."""
+        n = self.n
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n)
+        B = x.shape[0]
+        l, u = _arr(l, np.float64, n), _arr(u, np.float64, n)
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        sk = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8).reshape(B)
+        xo = np.zeros((B, n)); obj = np.zeros(B); status = np.zeros(B, np.int32); counts = np.zeros((B, 2), np.int32)
+        rc = lib().mipx_cube_search_batch(self._h, B, _ptr(x), _ptr(l), _ptr(u), _ptr(ii), len(ii), float(cutoff), float(tol),
+                                          float(ftol), int(max_columns), _ptr(sk), _ptr(xo), _ptr(obj), _ptr(status), _ptr(counts))
+        self.ctx.check(rc, 'mipx_cube_search_batch')
+        return dict(x=xo, obj=obj, status=status, counts=counts)
+
     def propagate_batch(self, l, u, integer_indices, cutoff=None, tol=PROPAGATION_TOL, max_rounds=DEFAULT_PROPAGATION_ROUNDS):
         """Bound propagation on host buffers (mipx_propagate_batch, include/mipx_prop.h): l, u (batch, n) boxes,
         cutoff None or an objective value no point above which is of interest.  Returns dict of l, u (batch, n),
@@ -1365,6 +1398,19 @@ class Tree:
         out = np.zeros(8, np.int64)
         self.problem.ctx.check(lib().mipx_tree_weighted_repair_stats(self._h, _ptr(out)), 'mipx_tree_weighted_repair_stats')
         return dict(zip(WREPAIR_STATS_KEYS, (int(v) for v in out)))
+
+    def set_cube_search(self, max_columns=True):
+        """Run the cube search beside the primal heuristic of every step, on the same LP points
+        (mipx_tree_set_cube_search, include/mipx_cube.h; True: DEFAULT_CUBE_SEARCH_COLUMNS columns at most; 0 or False:
+        off).  After set_heuristic."""
+        max_columns = DEFAULT_CUBE_SEARCH_COLUMNS if max_columns is True else int(max_columns)
+        self.problem.ctx.check(lib().mipx_tree_set_cube_search(self._h, max_columns), 'mipx_tree_set_cube_search')
+
+    def cube_search_stats(self):
+        """dict(points, found, none, columns, at_cap, incumbents, reserved6, kernel_us) (mipx_tree_cube_search_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_cube_search_stats(self._h, _ptr(out)), 'mipx_tree_cube_search_stats')
+        return dict(zip(CUBE_STATS_KEYS, (int(v) for v in out)))
 
     def set_objective_step(self, step):
         """Prune at one objective step below the incumbent (mipx_tree_set_objective_step, include/mipx_objstep.h):

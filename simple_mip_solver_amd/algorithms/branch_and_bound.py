@@ -126,7 +126,7 @@ class BranchAndBound(BaseAlgorithm):
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
                  propagate=None, reduced_cost=None, objective_step=None, local_search=None, fix_propagate=None,
-                 weighted_repair=None, **kwargs):
+                 weighted_repair=None, cube_search=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -238,7 +238,15 @@ class BranchAndBound(BaseAlgorithm):
         every row carries a weight, and where no move lowers the weighted violation the weights of the violated rows
         go up by one, at most that many moves and bumps per point (True: 256).  A point it ends feasible is lifted
         by the heuristic, goes through local_search when that is on, and competes for the step's incumbent.
-        Inherited by restart() with primal_heuristic.  Counters: `weighted_repair_stats`."""
+        Inherited by restart() with primal_heuristic.  Counters: `weighted_repair_stats`.
+        cube_search (extension; needs primal_heuristic; default None = off): True or a number of columns from 1 to
+        20.  In every step the heuristic runs in, the same LP points go through a cube search on the GPU
+        (include/mipx_cube.h): the at most that many most fractional integer columns (True: 16) are rounded down
+        and up in every combination, every other integer column held where the rounding puts it, and the best
+        combination that satisfies every row and lies below the cutoff is the point.  It is lifted by the
+        heuristic, goes through local_search when that is on, and competes for the step's incumbent beside the
+        heuristic's points and those of fix_propagate or weighted_repair.  Inherited by restart() with
+        primal_heuristic.  Counters: `cube_search_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -249,7 +257,8 @@ class BranchAndBound(BaseAlgorithm):
         self._given = dict(node_limit=node_limit, mip_gap=mip_gap, logging=logging, max_run_time=max_run_time,
                            frontier_batch=frontier_batch, pool_capacity=pool_capacity, anchor=anchor, dive=dive,
                            host_spill=host_spill, tree_record=tree_record, primal_heuristic=primal_heuristic,
-                           local_search=local_search, fix_propagate=fix_propagate, weighted_repair=weighted_repair)
+                           local_search=local_search, fix_propagate=fix_propagate, weighted_repair=weighted_repair,
+                           cube_search=cube_search)
         self._given_kwargs = dict(kwargs)
         self.restart_stats = None
         self.lp_batch = lp_batch
@@ -365,6 +374,13 @@ class BranchAndBound(BaseAlgorithm):
             'feasible on, and running one behind the other is not built: choose one)'
         self._weighted_repair = weighted_repair
         self.weighted_repair_stats = None
+        if not (cube_search is None or cube_search is True or (
+                isinstance(cube_search, int) and not isinstance(cube_search, bool) and 1 <= cube_search <= 20)):
+            raise ValueError('cube_search is None, True or a number of columns from 1 to 20')
+        if cube_search is not None and primal_heuristic is None:
+            raise ValueError('cube_search needs primal_heuristic (it runs on the LP points the heuristic takes)')
+        self._cube_search = cube_search
+        self.cube_search_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -550,6 +566,8 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_fix_propagate(self._fix_propagate)
             if self._weighted_repair:
                 self._native.set_weighted_repair(self._weighted_repair)
+            if self._cube_search:
+                self._native.set_cube_search(self._cube_search)
             if self._objective_step:
                 self._native.set_objective_step(self._objective_step)
             if self._propagate:
@@ -627,6 +645,8 @@ class BranchAndBound(BaseAlgorithm):
             self.fix_propagate_stats = self._native.fix_propagate_stats()
         if self._weighted_repair:
             self.weighted_repair_stats = self._native.weighted_repair_stats()
+        if self._cube_search:
+            self.cube_search_stats = self._native.cube_search_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')
@@ -634,7 +654,7 @@ class BranchAndBound(BaseAlgorithm):
                 self._kwargs[key] = self._native_totals0.get(key, 0) + value
 
     _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive', 'primal_heuristic',
-                          'local_search', 'fix_propagate', 'weighted_repair')
+                          'local_search', 'fix_propagate', 'weighted_repair', 'cube_search')
 
     def restart(self, b, **overrides):
         """A new, unsolved BranchAndBound for the same A, c, bounds and integer indices at the right-hand side
@@ -645,8 +665,8 @@ class BranchAndBound(BaseAlgorithm):
         find_parameterized_dual_bound (a CyLPArray of the constraint's shape, negated with the same warning if
         the constraints were flipped at instantiation).  Same Node class and keyword options; overrides may
         change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor, dive,
-        primal_heuristic, local_search, fix_propagate and weighted_repair (the last three run on the heuristic's
-        points: an override that turns primal_heuristic off turns the inherited ones off with it).
+        primal_heuristic, local_search, fix_propagate, weighted_repair and cube_search (the last four run on the
+        heuristic's points: an override that turns primal_heuristic off turns the inherited ones off with it).
         Needs frontier_batch and tree_record=True and a solve() before; not with comm; the restarted search
         records no dual function.  `restart_stats` of the new search reports the seeding."""
         assert self.frontier_batch is not None and self._tree_record, \
@@ -669,6 +689,8 @@ class BranchAndBound(BaseAlgorithm):
             opts['fix_propagate'] = None   # (and so does the dive)
         if not opts.get('primal_heuristic') and 'weighted_repair' not in overrides:
             opts['weighted_repair'] = None   # (and the weighted repair)
+        if not opts.get('primal_heuristic') and 'cube_search' not in overrides:
+            opts['cube_search'] = None   # (and the cube search)
         assert isinstance(opts['frontier_batch'], int) and 0 < opts['frontier_batch'] <= self.frontier_batch, \
             'a restarted search steps with at most the frontier_batch of its source'
         if self._swapped_constraint_direction:
@@ -711,6 +733,8 @@ class BranchAndBound(BaseAlgorithm):
             self._native.set_fix_propagate(self._fix_propagate)
         if self._weighted_repair:
             self._native.set_weighted_repair(self._weighted_repair)
+        if self._cube_search:
+            self._native.set_cube_search(self._cube_search)
         self.restart_stats = self._native.restart_stats()
         self._kwargs['next_node_idx'] = source._kwargs['next_node_idx']
 

@@ -137,6 +137,26 @@ struct WrOut {
     }
 };
 
+// Cube search output beside the heuristic's, cap points (the points themselves lie in a block of their own, not in
+// the heuristic's slots): [obj] (f64: the picked code's, then the lifted one) [status] (i32) [counts: k, code per
+// point] (i32), what the heuristic's pass over the FOUND points gives [lift_status | lift_moves: repair, lift per
+// point] (i32), and what the local search gives on those [ls_status | ls_moves: singles, pairs per point] (i32).
+struct CubeOut {
+    size_t obj, status, counts, lift_status, lift_moves, ls_status, ls_moves, end;
+    explicit CubeOut(size_t cap)
+        : obj(0), status(8 * cap), counts(status + 4 * cap), lift_status(counts + 8 * cap), lift_moves(lift_status + 4 * cap),
+          ls_status(lift_moves + 8 * cap), ls_moves(ls_status + 4 * cap), end(ls_moves + 8 * cap) {}
+    size_t bytes() const { return end; }
+    template <class Base> struct View {
+        Like<double, Base> *obj;
+        Like<int32_t, Base> *status, *counts, *lift_status, *lift_moves, *ls_status, *ls_moves;
+    };
+    template <class Base> View<Base> view(Base *b) const {
+        return {at<double>(b, obj), at<int32_t>(b, status), at<int32_t>(b, counts), at<int32_t>(b, lift_status),
+                at<int32_t>(b, lift_moves), at<int32_t>(b, ls_status), at<int32_t>(b, ls_moves)};
+    }
+};
+
 // Bound propagation output, cap nodes: [status | changed | rounds | capped], i32 each.
 struct PropOut {
     size_t status, changed, rounds, capped, end;

@@ -27,6 +27,7 @@
 #include "lsearch_kernels.hip.h"
 #include "fixprop_kernels.hip.h"
 #include "wrepair_kernels.hip.h"
+#include "cube_kernels.hip.h"
 #include "prop_kernels.hip.h"
 #include "rcfix_kernels.hip.h"
 #include "cglp_kernels.hip.h"
@@ -309,6 +310,7 @@ struct StepBuf {
     int ls_n = 0;     // local search: the points of this step it was launched on behind the heuristic (0: none)
     int fp_n = 0;     // fix-and-propagate dive: the points of this step it was launched on behind the heuristic (0: none)
     int wr_n = 0;     // weighted row repair: the points of this step it was launched on behind the heuristic (0: none)
+    int cube_n = 0;   // cube search: the points of this step it was launched on beside the heuristic (0: none)
     int prop_n = 0;   // bound propagation: the nodes of this step it was launched on (0: none)
     std::vector<int> rc_cnt;          // reduced-cost tightening: the parents it was launched on, per level, not yet
     hipStream_t rc_stream = nullptr;  // collected (empty: none), and the stream the launches went to
@@ -432,6 +434,21 @@ struct WrState {
     hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
     int64_t tried = 0, feasible = 0, capped = 0, moves = 0, bumps = 0, installed = 0;
     double us = 0.0;                 // device time of wrepair_steps and of the lift behind it
+};
+
+// Cube search beside the heuristic (include/mipx_cube.h): the column cap, the launch's workspace (mipx::CubeWs; one,
+// the launches are queued on one stream) and, per step buffer, the cube points -- a block of their own: the
+// heuristic's slots may hold feasible points already -- and what comes down with each step (step_layout::CubeOut).
+struct CubeState {
+    bool on = false;
+    int max_columns = 0;
+    int cap = 0, ws_columns = 0;     // points the step buffers are laid out for (the heuristic's cap); K the workspace is for
+    char *d_ws = nullptr;
+    double *d_x[3] = {nullptr, nullptr, nullptr};
+    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    int64_t tried = 0, found = 0, none = 0, columns = 0, at_cap = 0, installed = 0;
+    double us = 0.0;                 // device time of the three kernels and of the lift behind them
 };
 
 // Objective step (include/mipx_objstep.h): the step and the counters.
@@ -600,6 +617,7 @@ struct mipx_tree {
     LsState ls;
     FpState fp;
     WrState wr;
+    CubeState cu;
     ObjStepState os;
     PropState pg;
     RcState rc;
@@ -826,10 +844,42 @@ int wr_launch(const mipx_problem *p, hipStream_t st, int batch, const double *d_
     return MIPX_OK;
 }
 
+// One run of the cube search over `batch` points in device memory, queued on `st`: cube_prepare, cube_enumerate and
+// cube_pick, one behind the other (d_ws: a block of mipx::CubeWs(batch, m, max_columns).bytes() at least; d_lp_status:
+// null, or per point the status of its node LP -- a point whose entry is not 0 is skipped; d_x_out is not d_x).
+int cube_launch(const mipx_problem *p, hipStream_t st, int batch, const double *d_x, const double *d_l, const double *d_u,
+                const int32_t *d_int_idx, int n_int, double cutoff, double tol, double ftol, int max_columns,
+                const uint8_t *d_skip, const int32_t *d_lp_status, char *d_ws, double *d_x_out, double *d_obj,
+                int32_t *d_status, int32_t *d_counts) {
+    mipx_ctx *ctx = p->ctx;
+    if (p->m > mipx::kCubeMax || p->n > mipx::kCubeMax) return fail(ctx, MIPX_ETOOBIG, "cube search: more than 1024 rows or columns");
+    if (max_columns < 1 || max_columns > mipx::kCubeMaxK) return fail(ctx, MIPX_EINVAL, "cube search: max_columns outside 1..20");
+    if (batch <= 0) return MIPX_OK;
+    const mipx::CubeWs w((size_t)batch, (size_t)p->m, max_columns);
+    mipx::CubeArgs a;
+    a.m = p->m; a.n = p->n; a.n_int = n_int; a.K = max_columns; a.nchunks = mipx::cube_chunks(max_columns); a.p0 = 0;
+    a.tol = tol; a.ftol = ftol; a.cutoff = cutoff;
+    a.A = p->dA; a.b = p->db; a.c = p->dc; a.l = d_l; a.u = d_u; a.int_idx = d_int_idx;
+    a.x = d_x; a.skip = d_skip; a.lp_status = d_lp_status;
+    a.ws_s = (double *)(d_ws + w.s); a.ws_obj0 = (double *)(d_ws + w.obj0); a.ws_pobj = (double *)(d_ws + w.pobj);
+    a.ws_kf = (int32_t *)(d_ws + w.kf); a.ws_pcode = (int32_t *)(d_ws + w.pcode);
+    a.x_out = d_x_out; a.obj_out = d_obj; a.status_out = d_status; a.counts_out = d_counts;
+    hipLaunchKernelGGL(mipx::cube_prepare, dim3((unsigned)batch), dim3(mipx::kCubeNT), 0, st, a);
+    for (a.p0 = 0; a.p0 < batch; a.p0 += mipx::kCubeGridY)   // (the points lie in the grid's y, which ends at 65535)
+        hipLaunchKernelGGL(mipx::cube_enumerate, dim3((unsigned)a.nchunks, (unsigned)std::min(batch - a.p0, mipx::kCubeGridY)),
+                           dim3(mipx::kCubeNT), 0, st, a);
+    a.p0 = 0;
+    hipLaunchKernelGGL(mipx::cube_pick, dim3((unsigned)batch), dim3(mipx::kCubeNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
 // The step's node LP solutions (level 0, the first positions) through the heuristic, behind its node LPs; the points
 // it did not end feasible on through the fix-and-propagate dive, whose feasible points take their place and go through
 // the heuristic once more (the lift), or through the weighted row repair in the same way (one of the two at most); and
-// the feasible points of both through the local search, in place.
+// the feasible points of both through the local search, in place.  With the cube search the same LP points go through
+// it as well, whatever the rounding made of them: its points lie in a block of their own, are lifted by the heuristic
+// there and go through the local search there.
 int heur_step_launch(mipx_tree *t, StepBuf &S) {
     HeurState &hr = t->hr;
     S.heur_n = 0;
@@ -877,6 +927,22 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
         HIP_TRY(ctx, hipEventRecord(wr.e1[bi], st));
         S.wr_n = P;
     }
+    S.cube_n = 0;
+    CubeState &cu = t->cu;
+    const auto co = step_layout::CubeOut((size_t)(cu.on ? cu.cap : 0)).view(cu.on ? cu.d_out[bi] : nullptr);
+    if (cu.on) {
+        // the LP points again, gated by the node LP's status as the heuristic is; a FOUND point goes through the heuristic
+        // in place (rounding an integral point changes nothing and its repair is empty: the lift), gated by the cube's status
+        HIP_TRY(ctx, hipEventRecord(cu.e0[bi], st));
+        int crc = cube_launch(t->prob, st, P, S.d_x, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, tree_cutoff(t), hr.tol,
+                              mipx::kVarEps, cu.max_columns, nullptr, S.d.status, cu.d_ws, cu.d_x[bi], co.obj, co.status, co.counts);
+        if (crc) return crc;
+        crc = heur_launch(t->prob, st, P, cu.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
+                          nullptr, co.status, cu.d_x[bi], co.obj, co.lift_status, co.lift_moves);
+        if (crc) return crc;
+        HIP_TRY(ctx, hipEventRecord(cu.e1[bi], st));
+        S.cube_n = P;
+    }
     LsState &ls = t->ls;
     if (ls.on) {
         const auto lo = step_layout::LsOut((size_t)ls.cap).view(ls.d_out[bi]);
@@ -893,6 +959,11 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
             const int wrc = ls_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
                                       ls.max_moves, nullptr, wo.lift_status, hr.d_x[bi], wo.obj, wo.ls_status, wo.ls_moves);
             if (wrc) return wrc;
+        }
+        if (cu.on) {   // ... and the lifted cube points, in their own block
+            const int crc = ls_launch(t->prob, st, P, cu.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
+                                      ls.max_moves, nullptr, co.lift_status, cu.d_x[bi], co.obj, co.ls_status, co.ls_moves);
+            if (crc) return crc;
         }
         HIP_TRY(ctx, hipEventRecord(ls.e1[bi], st));
         S.ls_n = P;
@@ -998,8 +1069,41 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
             }
         }
     }
+    // cube search: its counters, and its points (a family of their own, in their own block)
+    CubeState &cu = t->cu;
+    const int CP = S.cube_n;
+    S.cube_n = 0;
+    const double *cu_obj = nullptr;
+    const int32_t *cu_ok = nullptr, *cu_ls_moves = nullptr;
+    if (CP > 0) {
+        const step_layout::CubeOut clay((size_t)cu.cap);
+        if ((rc = tree_d2h(t, cu.h_out[bi], cu.d_out[bi], clay.bytes()))) return rc;
+        if (hipEventElapsedTime(&ms, cu.e0[bi], cu.e1[bi]) == hipSuccess) cu.us += 1000.0 * ms;
+        const auto co = clay.view((const char *)cu.h_out[bi]);
+        cu_obj = co.obj;
+        cu_ok = co.lift_status;   // (0: the cube held a point and the heuristic's pass lifted it)
+        for (int k = 0; k < CP; k++) {
+            if (co.status[k] == MIPX_CUBE_SKIPPED) continue;
+            cu.tried++;
+            cu.columns += co.counts[2 * k];
+            if (co.counts[2 * k] == cu.max_columns) cu.at_cap++;
+            if (co.status[k] == MIPX_CUBE_FOUND) cu.found++;
+            if (co.status[k] == MIPX_CUBE_NONE) cu.none++;
+        }
+        if (LP > 0) {
+            cu_ls_moves = co.ls_moves;
+            for (int k = 0; k < CP; k++) {
+                if (co.ls_status[k] == MIPX_LS_SKIPPED) continue;
+                ls.run++;
+                ls.singles += co.ls_moves[2 * k];
+                ls.pairs += co.ls_moves[2 * k + 1];
+                if (co.ls_moves[2 * k] + co.ls_moves[2 * k + 1] > 0) ls.improved++;
+                if (co.ls_status[k] == MIPX_LS_CAPPED) ls.capped++;
+            }
+        }
+    }
     int best = -1;
-    bool best_fp = false;
+    bool best_fp = false, best_cube = false;
     double best_obj = 0.0;
     for (int k = 0; k < P; k++) {
         if (fp_ok && status[k] != MIPX_HEUR_SKIPPED && status[k] != MIPX_HEUR_FEASIBLE && fp_ok[k] == MIPX_HEUR_FEASIBLE &&
@@ -1016,16 +1120,23 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         hr.feasible++;
         if (best < 0 || obj[k] < best_obj) { best = k; best_fp = false; best_obj = obj[k]; }
     }
+    // (the cube's points behind the others: a tie goes to the earlier family, then to the lowest position)
+    for (int k = 0; k < CP; k++)
+        if (cu_ok[k] == MIPX_HEUR_FEASIBLE && (best < 0 || cu_obj[k] < best_obj)) {
+            best = k; best_fp = false; best_cube = true; best_obj = cu_obj[k];
+        }
     if (best >= 0 && best_obj < t->primal) {
         t->primal = best_obj;
-        if ((rc = tree_d2h(t, t->best_x.data(), hr.d_x[bi] + (size_t)best * n, (size_t)n * 8))) return rc;
+        const double *from = best_cube ? cu.d_x[bi] : hr.d_x[bi];   // (the block that won)
+        if ((rc = tree_d2h(t, t->best_x.data(), from + (size_t)best * n, (size_t)n * 8))) return rc;
         t->have_x = true;
         // (the point is a closed leaf of value obj: without it no closed leaf holds the incumbent's value, and the
         // dual bound of an emptied queue would end above the incumbent instead of on it)
         t->closed_min = std::fmin(t->closed_min, best_obj);
         hr.installed++;
         if (best_fp) (WP > 0 ? wr.installed : fp.installed)++;
-        const int32_t *lm = best_fp ? fp_ls_moves : ls_moves;
+        if (best_cube) cu.installed++;
+        const int32_t *lm = best_cube ? cu_ls_moves : best_fp ? fp_ls_moves : ls_moves;
         if (lm && lm[2 * best] + lm[2 * best + 1] > 0) ls.installed++;
     }
     return MIPX_OK;
@@ -3381,6 +3492,17 @@ void mipx_tree_destroy(mipx_tree *t) {
         }
     }
     {
+        CubeState &cu = t->cu;
+        if (cu.d_ws) (void)hipFree(cu.d_ws);
+        for (int k = 0; k < 3; k++) {
+            if (cu.d_x[k]) (void)hipFree(cu.d_x[k]);
+            if (cu.d_out[k]) (void)hipFree(cu.d_out[k]);
+            if (cu.h_out[k]) (void)hipHostFree(cu.h_out[k]);
+            if (cu.e0[k]) (void)hipEventDestroy(cu.e0[k]);
+            if (cu.e1[k]) (void)hipEventDestroy(cu.e1[k]);
+        }
+    }
+    {
         RcState &rs = t->rc;
         for (int k = 0; k < 3; k++) {
             if (rs.d_y[k]) (void)hipFree(rs.d_y[k]);
@@ -4215,4 +4337,5 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "lsearch_api.hip.h"
 #include "fixprop_api.hip.h"
 #include "wrepair_api.hip.h"
+#include "cube_api.hip.h"
 #include "objstep_api.hip.h"
