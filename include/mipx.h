@@ -542,5 +542,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_fixprop.h" /* fix-and-propagate dive behind the primal heuristic on the GPU */
 #include "mipx_wrepair.h" /* weighted row repair behind the primal heuristic on the GPU */
 #include "mipx_cube.h" /* cube search beside the primal heuristic on the GPU */
+#include "mipx_complete.h" /* heuristic points completed over the continuous columns by a batched LP */
 
 #endif /* MIPX_H */

@@ -375,6 +375,19 @@ CUBE_STATUS = {0: 'found', 1: 'none', 3: 'skipped'}
 DEFAULT_CUBE_SEARCH_COLUMNS = 16
 MAX_CUBE_SEARCH_COLUMNS = 20
 
+# ... and those of include/mipx_complete.h (heuristic points completed over the continuous columns by a batched LP),
+# which mipx.h includes (tests/test_completion_abi.py checks them against that header)
+_COMPLETE_SIGNATURES = {
+    'mipx_complete_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _vp, _d, _vp] + [_vp] * 4),
+    'mipx_tree_set_completion': (_i, [_vp, _i]),
+    'mipx_tree_completion_stats': (_i, [_vp, _vp]),
+}
+COMPLETE_SYMBOLS = list(_COMPLETE_SIGNATURES)
+COMPLETE_STATS_KEYS = ('points', 'completed', 'infeasible', 'failed', 'rescued', 'incumbents', 'pivots', 'kernel_us')
+COMPLETE_STATUS = {0: 'completed', 1: 'infeasible', 2: 'limit', 3: 'skipped', 4: 'rejected'}
+# the tolerance a completed point is checked with, in the engine and by default in complete_batch
+DEFAULT_COMPLETION_TOL = 1e-6
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -394,7 +407,7 @@ def lib():
                                       list(_PROP_SIGNATURES.items()) + list(_RCFIX_SIGNATURES.items()) +
                                       list(_LSEARCH_SIGNATURES.items()) + list(_OBJSTEP_SIGNATURES.items()) +
                                       list(_FIXPROP_SIGNATURES.items()) + list(_WREPAIR_SIGNATURES.items()) +
-                                      list(_CUBE_SIGNATURES.items())):
+                                      list(_CUBE_SIGNATURES.items()) + list(_COMPLETE_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -934,6 +947,24 @@ class Problem:
         self.ctx.check(rc, 'mipx_cube_search_batch')
         return dict(x=xo, obj=obj, status=status, counts=counts)
 
+    def complete_batch(self, x, l, u, integer_indices, vstat=None, ctol=DEFAULT_COMPLETION_TOL, skip=None):
+        """Completion over the continuous columns on host buffers (mipx_complete_batch, include/mipx_complete.h): x
+        (batch, n) points whose integer columns are held while one batched LP is solved over the others, l, u the
+        bounds (n each), vstat None (cold) or (batch, n + m) basis codes to start from, skip an optional (batch,)
+        mask.  Returns dict of x (batch, n), obj, status (COMPLETE_STATUS codes) and pivots."""
+        n = self.n
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n)
+        B = x.shape[0]
+        l, u = _arr(l, np.float64, n), _arr(u, np.float64, n)
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        vs = None if vstat is None else np.ascontiguousarray(vstat, dtype=np.int8).reshape(B, n + self.m)
+        sk = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8).reshape(B)
+        xo = np.zeros((B, n)); obj = np.zeros(B); status = np.zeros(B, np.int32); pivots = np.zeros(B, np.int32)
+        rc = lib().mipx_complete_batch(self._h, B, _ptr(x), _ptr(l), _ptr(u), _ptr(ii), len(ii), _ptr(vs), float(ctol), _ptr(sk),
+                                       _ptr(xo), _ptr(obj), _ptr(status), _ptr(pivots))
+        self.ctx.check(rc, 'mipx_complete_batch')
+        return dict(x=xo, obj=obj, status=status, pivots=pivots)
+
     def propagate_batch(self, l, u, integer_indices, cutoff=None, tol=PROPAGATION_TOL, max_rounds=DEFAULT_PROPAGATION_ROUNDS):
         """Bound propagation on host buffers (mipx_propagate_batch, include/mipx_prop.h): l, u (batch, n) boxes,
         cutoff None or an objective value no point above which is of interest.  Returns dict of l, u (batch, n),
@@ -1411,6 +1442,17 @@ class Tree:
         out = np.zeros(8, np.int64)
         self.problem.ctx.check(lib().mipx_tree_cube_search_stats(self._h, _ptr(out)), 'mipx_tree_cube_search_stats')
         return dict(zip(CUBE_STATS_KEYS, (int(v) for v in out)))
+
+    def set_completion(self, on=True):
+        """Complete the points the heuristics of every step end on over the continuous columns, by one batched LP per
+        step (mipx_tree_set_completion, include/mipx_complete.h; False: off).  After set_heuristic."""
+        self.problem.ctx.check(lib().mipx_tree_set_completion(self._h, 1 if on else 0), 'mipx_tree_set_completion')
+
+    def completion_stats(self):
+        """dict(points, completed, infeasible, failed, rescued, incumbents, pivots, kernel_us) (mipx_tree_completion_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_completion_stats(self._h, _ptr(out)), 'mipx_tree_completion_stats')
+        return dict(zip(COMPLETE_STATS_KEYS, (int(v) for v in out)))
 
     def set_objective_step(self, step):
         """Prune at one objective step below the incumbent (mipx_tree_set_objective_step, include/mipx_objstep.h):

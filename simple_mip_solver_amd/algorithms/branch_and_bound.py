@@ -126,7 +126,7 @@ class BranchAndBound(BaseAlgorithm):
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
                  propagate=None, reduced_cost=None, objective_step=None, local_search=None, fix_propagate=None,
-                 weighted_repair=None, cube_search=None, **kwargs):
+                 weighted_repair=None, cube_search=None, complete_continuous=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -246,7 +246,14 @@ class BranchAndBound(BaseAlgorithm):
         combination that satisfies every row and lies below the cutoff is the point.  It is lifted by the
         heuristic, goes through local_search when that is on, and competes for the step's incumbent beside the
         heuristic's points and those of fix_propagate or weighted_repair.  Inherited by restart() with
-        primal_heuristic.  Counters: `cube_search_stats`."""
+        primal_heuristic.  Counters: `cube_search_stats`.
+        complete_continuous (extension; needs primal_heuristic; default None = off): True.  The heuristics above move
+        integer columns only and leave a continuous column at its value in the node's LP point.  With this option
+        every point they end on, feasible or not, has its integer columns held and the LP over the other columns
+        solved on the GPU (include/mipx_complete.h), all points of a step in one launch, warm from the basis of the
+        node LP the point came from.  A completed point (every row within 1e-6) takes its source's place in the
+        contest for the step's incumbent.  On a model without continuous columns nothing is launched.  Inherited by
+        restart() with primal_heuristic.  Counters: `completion_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -258,7 +265,7 @@ class BranchAndBound(BaseAlgorithm):
                            frontier_batch=frontier_batch, pool_capacity=pool_capacity, anchor=anchor, dive=dive,
                            host_spill=host_spill, tree_record=tree_record, primal_heuristic=primal_heuristic,
                            local_search=local_search, fix_propagate=fix_propagate, weighted_repair=weighted_repair,
-                           cube_search=cube_search)
+                           cube_search=cube_search, complete_continuous=complete_continuous)
         self._given_kwargs = dict(kwargs)
         self.restart_stats = None
         self.lp_batch = lp_batch
@@ -381,6 +388,12 @@ class BranchAndBound(BaseAlgorithm):
             raise ValueError('cube_search needs primal_heuristic (it runs on the LP points the heuristic takes)')
         self._cube_search = cube_search
         self.cube_search_stats = None
+        if not (complete_continuous is None or complete_continuous is True):
+            raise ValueError('complete_continuous is None or True')
+        if complete_continuous is not None and primal_heuristic is None:
+            raise ValueError('complete_continuous needs primal_heuristic (it completes the points the heuristics end on)')
+        self._complete_continuous = complete_continuous
+        self.completion_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -568,6 +581,8 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_weighted_repair(self._weighted_repair)
             if self._cube_search:
                 self._native.set_cube_search(self._cube_search)
+            if self._complete_continuous:
+                self._native.set_completion(True)
             if self._objective_step:
                 self._native.set_objective_step(self._objective_step)
             if self._propagate:
@@ -647,6 +662,8 @@ class BranchAndBound(BaseAlgorithm):
             self.weighted_repair_stats = self._native.weighted_repair_stats()
         if self._cube_search:
             self.cube_search_stats = self._native.cube_search_stats()
+        if self._complete_continuous:
+            self.completion_stats = self._native.completion_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')
@@ -654,7 +671,7 @@ class BranchAndBound(BaseAlgorithm):
                 self._kwargs[key] = self._native_totals0.get(key, 0) + value
 
     _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive', 'primal_heuristic',
-                          'local_search', 'fix_propagate', 'weighted_repair', 'cube_search')
+                          'local_search', 'fix_propagate', 'weighted_repair', 'cube_search', 'complete_continuous')
 
     def restart(self, b, **overrides):
         """A new, unsolved BranchAndBound for the same A, c, bounds and integer indices at the right-hand side
@@ -665,8 +682,8 @@ class BranchAndBound(BaseAlgorithm):
         find_parameterized_dual_bound (a CyLPArray of the constraint's shape, negated with the same warning if
         the constraints were flipped at instantiation).  Same Node class and keyword options; overrides may
         change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor, dive,
-        primal_heuristic, local_search, fix_propagate, weighted_repair and cube_search (the last four run on the
-        heuristic's points: an override that turns primal_heuristic off turns the inherited ones off with it).
+        primal_heuristic, local_search, fix_propagate, weighted_repair, cube_search and complete_continuous (the last
+        five run on the heuristic's points: an override that turns primal_heuristic off turns the inherited ones off with it).
         Needs frontier_batch and tree_record=True and a solve() before; not with comm; the restarted search
         records no dual function.  `restart_stats` of the new search reports the seeding."""
         assert self.frontier_batch is not None and self._tree_record, \
@@ -691,6 +708,8 @@ class BranchAndBound(BaseAlgorithm):
             opts['weighted_repair'] = None   # (and the weighted repair)
         if not opts.get('primal_heuristic') and 'cube_search' not in overrides:
             opts['cube_search'] = None   # (and the cube search)
+        if not opts.get('primal_heuristic') and 'complete_continuous' not in overrides:
+            opts['complete_continuous'] = None   # (and the completion)
         assert isinstance(opts['frontier_batch'], int) and 0 < opts['frontier_batch'] <= self.frontier_batch, \
             'a restarted search steps with at most the frontier_batch of its source'
         if self._swapped_constraint_direction:
@@ -735,6 +754,8 @@ class BranchAndBound(BaseAlgorithm):
             self._native.set_weighted_repair(self._weighted_repair)
         if self._cube_search:
             self._native.set_cube_search(self._cube_search)
+        if self._complete_continuous:
+            self._native.set_completion(True)
         self.restart_stats = self._native.restart_stats()
         self._kwargs['next_node_idx'] = source._kwargs['next_node_idx']
 

@@ -157,6 +157,23 @@ struct CubeOut {
     }
 };
 
+// Completion output (include/mipx_complete.h), room for two blocks of cap points: [obj] (f64) [status] (i32) [pivots]
+// (i32), 2 cap entries each.  A step of P <= cap points uses the first P entries of a field for the heuristic's block
+// and, with the cube search on, the next P for the cube's (the launch's positions).  The completed points
+// themselves lie in a block of their own, in the same order.
+struct CompOut {
+    size_t obj, status, pivots, end;
+    explicit CompOut(size_t cap) : obj(0), status(16 * cap), pivots(status + 8 * cap), end(pivots + 8 * cap) {}
+    size_t bytes() const { return end; }
+    template <class Base> struct View {
+        Like<double, Base> *obj;
+        Like<int32_t, Base> *status, *pivots;
+    };
+    template <class Base> View<Base> view(Base *b) const {
+        return {at<double>(b, obj), at<int32_t>(b, status), at<int32_t>(b, pivots)};
+    }
+};
+
 // Bound propagation output, cap nodes: [status | changed | rounds | capped], i32 each.
 struct PropOut {
     size_t status, changed, rounds, capped, end;

@@ -28,6 +28,7 @@
 #include "fixprop_kernels.hip.h"
 #include "wrepair_kernels.hip.h"
 #include "cube_kernels.hip.h"
+#include "complete_kernels.hip.h"
 #include "prop_kernels.hip.h"
 #include "rcfix_kernels.hip.h"
 #include "cglp_kernels.hip.h"
@@ -311,6 +312,8 @@ struct StepBuf {
     int fp_n = 0;     // fix-and-propagate dive: the points of this step it was launched on behind the heuristic (0: none)
     int wr_n = 0;     // weighted row repair: the points of this step it was launched on behind the heuristic (0: none)
     int cube_n = 0;   // cube search: the points of this step it was launched on beside the heuristic (0: none)
+    int comp_n = 0;   // completion: the points per block of this step it was launched on behind the heuristics (0: none)
+    bool comp_cube = false;   // ... and whether the cube's block went with the heuristic's
     int prop_n = 0;   // bound propagation: the nodes of this step it was launched on (0: none)
     std::vector<int> rc_cnt;          // reduced-cost tightening: the parents it was launched on, per level, not yet
     hipStream_t rc_stream = nullptr;  // collected (empty: none), and the stream the launches went to
@@ -449,6 +452,22 @@ struct CubeState {
     hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
     int64_t tried = 0, found = 0, none = 0, columns = 0, at_cap = 0, installed = 0;
     double us = 0.0;                 // device time of the three kernels and of the lift behind them
+};
+
+// Completion over the continuous columns (include/mipx_complete.h): the tolerance, the launch's workspace
+// (mipx::CompWs for 2 cap points; one, the launches are queued on one stream) and, per step buffer, the completed
+// points -- a block of their own, the heuristic's cap points and then the cube's -- and what comes down with each step
+// (step_layout::CompOut).
+struct CompState {
+    bool on = false;
+    double ctol = 1e-6;
+    int cap = 0;                     // points per block the step buffers are laid out for (the heuristic's cap)
+    char *d_ws = nullptr;
+    double *d_x[3] = {nullptr, nullptr, nullptr};
+    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    int64_t tried = 0, completed = 0, infeasible = 0, failed = 0, rescued = 0, installed = 0, pivots = 0;
+    double us = 0.0;                 // device time of the two kernels and the LP launch between them
 };
 
 // Objective step (include/mipx_objstep.h): the step and the counters.
@@ -618,6 +637,7 @@ struct mipx_tree {
     FpState fp;
     WrState wr;
     CubeState cu;
+    CompState cc;
     ObjStepState os;
     PropState pg;
     RcState rc;
@@ -874,6 +894,59 @@ int cube_launch(const mipx_problem *p, hipStream_t st, int batch, const double *
     return MIPX_OK;
 }
 
+// One block of points of a completion launch: `count` points in device memory, with their optional skip bytes, gate
+// (a heuristic's status per point: 3 is skipped, and with gate_strict everything but 0) and basis codes (n + m per
+// point), all indexed from the block's start.
+struct CompSrc {
+    const double *x;
+    const uint8_t *skip;
+    const int32_t *gate;
+    bool gate_strict;
+    const int8_t *vstat;
+    int count;
+};
+
+// One completion (include/mipx_complete.h) of the points of `nsrc` blocks, queued on `st`: complete_prepare per block,
+// ONE node-LP launch over all of them, complete_finish.  The outputs are indexed by position: the blocks behind one
+// another (d_ws: mipx::CompWs(total, m, n).bytes() at least; d_x_out is none of the blocks).  The LP launch always
+// carries basis codes (all 0 where a block has none: a cold start), so it never takes launch_root_coop's path, which
+// would have the host wait; the problem's anchor is not used.
+int comp_launch(mipx_problem *p, hipStream_t st, const CompSrc *src, int nsrc, const double *d_l, const double *d_u,
+                const int32_t *d_int_idx, int n_int, double ctol, char *d_ws, double *d_x_out, double *d_obj,
+                int32_t *d_status, int32_t *d_pivots) {
+    mipx_ctx *ctx = p->ctx;
+    if (p->m > mipx::kCompMax || p->n > mipx::kCompMax) return fail(ctx, MIPX_ETOOBIG, "completion: more than 1024 rows or columns");
+    int total = 0;
+    for (int k = 0; k < nsrc; k++) total += src[k].count > 0 ? src[k].count : 0;
+    if (total <= 0) return MIPX_OK;
+    const mipx::CompWs w((size_t)total, (size_t)p->m, (size_t)p->n);
+    mipx::CompArgs a;
+    a.m = p->m; a.n = p->n; a.n_int = n_int; a.p0 = 0; a.ctol = ctol;
+    a.A = p->dA; a.b = p->db; a.c = p->dc; a.l = d_l; a.u = d_u; a.int_idx = d_int_idx;
+    a.x = nullptr; a.skip = nullptr; a.gate = nullptr; a.gate_strict = 0; a.vstat = nullptr;
+    a.ws_L = (double *)(d_ws + w.L); a.ws_U = (double *)(d_ws + w.U); a.ws_x = (const double *)(d_ws + w.x);
+    a.ws_skipped = (int32_t *)(d_ws + w.skipped); a.ws_lp_status = (const int32_t *)(d_ws + w.lp_status);
+    a.ws_pivots = (const int32_t *)(d_ws + w.pivots); a.ws_vstat = (int8_t *)(d_ws + w.vstat);
+    a.x_out = d_x_out; a.obj_out = d_obj; a.status_out = d_status; a.pivots_out = d_pivots;
+    for (int k = 0; k < nsrc; k++) {
+        if (src[k].count <= 0) continue;
+        a.x = src[k].x; a.skip = src[k].skip; a.gate = src[k].gate; a.gate_strict = src[k].gate_strict ? 1 : 0; a.vstat = src[k].vstat;
+        hipLaunchKernelGGL(mipx::complete_prepare, dim3((unsigned)src[k].count), dim3(mipx::kCompNT), 0, st, a);
+        a.p0 += src[k].count;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    mipx::LpArgs g = problem_args(p, false);
+    g.l = a.ws_L; g.u = a.ws_U; g.vstat_in = a.ws_vstat; g.max_iter = 0;
+    g.status = (int32_t *)(d_ws + w.lp_status); g.x = (double *)(d_ws + w.x); g.npivots = (int32_t *)(d_ws + w.pivots);
+    g.batch = total;
+    const int rc = launch_lp_any(p, g, total, st);
+    if (rc) return rc;
+    a.p0 = 0;
+    hipLaunchKernelGGL(mipx::complete_finish, dim3((unsigned)total), dim3(mipx::kCompNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
 // The step's node LP solutions (level 0, the first positions) through the heuristic, behind its node LPs; the points
 // it did not end feasible on through the fix-and-propagate dive, whose feasible points take their place and go through
 // the heuristic once more (the lift), or through the weighted row repair in the same way (one of the two at most); and
@@ -967,6 +1040,25 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
         }
         HIP_TRY(ctx, hipEventRecord(ls.e1[bi], st));
         S.ls_n = P;
+    }
+    // completion: behind the last stage of every block, the heuristic's slots (its own points and those of the dive or
+    // the weighted repair) and the cube's FOUND points (a cube without a point leaves the LP point in its slot, which
+    // is nobody's point), in one LP launch; point k of either block starts from the final basis of node LP k, the LP
+    // whose solution it was made from (S.d_vout, level 0)
+    S.comp_n = 0;
+    S.comp_cube = false;
+    CompState &cc = t->cc;
+    if (cc.on && t->n_int < t->n) {
+        const auto qo = step_layout::CompOut((size_t)cc.cap).view(cc.d_out[bi]);
+        const CompSrc src[2] = {{hr.d_x[bi], nullptr, o.status, false, S.d_vout, P},
+                                {cu.on ? cu.d_x[bi] : nullptr, nullptr, co.status, true, S.d_vout, cu.on ? P : 0}};
+        HIP_TRY(ctx, hipEventRecord(cc.e0[bi], st));
+        const int qrc = comp_launch(t->prob, st, src, 2, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, cc.ctol, cc.d_ws,
+                                    cc.d_x[bi], qo.obj, qo.status, qo.pivots);
+        if (qrc) return qrc;
+        HIP_TRY(ctx, hipEventRecord(cc.e1[bi], st));
+        S.comp_n = P;
+        S.comp_cube = cu.on;
     }
     return MIPX_OK;
 }
@@ -1102,13 +1194,41 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
             }
         }
     }
+    // completion: its counters; a COMPLETED point stands in for its source point below, with the objective of its LP
+    CompState &cc = t->cc;
+    const int QP = S.comp_n;
+    const bool q_cube = S.comp_cube;
+    S.comp_n = 0;
+    S.comp_cube = false;
+    const double *q_obj = nullptr;
+    const int32_t *q_status = nullptr;
+    if (QP > 0) {
+        const step_layout::CompOut qlay((size_t)cc.cap);
+        if ((rc = tree_d2h(t, cc.h_out[bi], cc.d_out[bi], qlay.bytes()))) return rc;
+        if (hipEventElapsedTime(&ms, cc.e0[bi], cc.e1[bi]) == hipSuccess) cc.us += 1000.0 * ms;
+        const auto qo = qlay.view((const char *)cc.h_out[bi]);
+        q_obj = qo.obj;
+        q_status = qo.status;
+        for (int k = 0; k < (q_cube ? 2 : 1) * QP; k++) {
+            if (qo.status[k] == MIPX_COMPLETE_SKIPPED) continue;
+            cc.tried++;
+            cc.pivots += qo.pivots[k];
+            if (qo.status[k] == MIPX_COMPLETE_COMPLETED) cc.completed++;
+            else if (qo.status[k] == MIPX_COMPLETE_INFEASIBLE) cc.infeasible++;
+            else cc.failed++;
+        }
+    }
     int best = -1;
-    bool best_fp = false, best_cube = false;
+    bool best_fp = false, best_cube = false, best_comp = false;
     double best_obj = 0.0;
     for (int k = 0; k < P; k++) {
-        if (fp_ok && status[k] != MIPX_HEUR_SKIPPED && status[k] != MIPX_HEUR_FEASIBLE && fp_ok[k] == MIPX_HEUR_FEASIBLE &&
-            (best < 0 || fp_obj[k] < best_obj)) {
-            best = k; best_fp = true; best_obj = fp_obj[k];
+        const bool done = q_status && k < QP && q_status[k] == MIPX_COMPLETE_COMPLETED;   // (position k of the heuristic's block)
+        const bool own = status[k] == MIPX_HEUR_FEASIBLE;
+        const bool other = fp_ok && status[k] != MIPX_HEUR_SKIPPED && !own && fp_ok[k] == MIPX_HEUR_FEASIBLE;
+        if (done && !own && !other) cc.rescued++;
+        if (other || (done && !own)) {   // (the dive's or the repair's slot; a rescued point competes where they would)
+            const double v = done ? q_obj[k] : fp_obj[k];
+            if (best < 0 || v < best_obj) { best = k; best_fp = other; best_comp = done; best_obj = v; }
         }
         if (status[k] == MIPX_HEUR_SKIPPED) continue;
         hr.tried++;
@@ -1116,18 +1236,25 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         hr.lift += moves[2 * k + 1];
         if (status[k] == MIPX_HEUR_STUCK) hr.stuck++;
         if (status[k] == MIPX_HEUR_CAPPED) hr.capped++;
-        if (status[k] != MIPX_HEUR_FEASIBLE) continue;
+        if (!own) continue;
         hr.feasible++;
-        if (best < 0 || obj[k] < best_obj) { best = k; best_fp = false; best_obj = obj[k]; }
+        const double v = done ? q_obj[k] : obj[k];
+        if (best < 0 || v < best_obj) { best = k; best_fp = false; best_comp = done; best_obj = v; }
     }
     // (the cube's points behind the others: a tie goes to the earlier family, then to the lowest position)
-    for (int k = 0; k < CP; k++)
-        if (cu_ok[k] == MIPX_HEUR_FEASIBLE && (best < 0 || cu_obj[k] < best_obj)) {
-            best = k; best_fp = false; best_cube = true; best_obj = cu_obj[k];
-        }
+    for (int k = 0; k < CP; k++) {
+        const bool done = q_status && q_cube && k < QP && q_status[QP + k] == MIPX_COMPLETE_COMPLETED;
+        const bool own = cu_ok[k] == MIPX_HEUR_FEASIBLE;
+        if (done && !own) cc.rescued++;
+        if (!done && !own) continue;
+        const double v = done ? q_obj[QP + k] : cu_obj[k];
+        if (best < 0 || v < best_obj) { best = k; best_fp = false; best_cube = true; best_comp = done; best_obj = v; }
+    }
     if (best >= 0 && best_obj < t->primal) {
         t->primal = best_obj;
-        const double *from = best_cube ? cu.d_x[bi] : hr.d_x[bi];   // (the block that won)
+        // (the block that won: a completed point lies in the completion's, at its source's position)
+        const double *from = best_comp ? cc.d_x[bi] + (best_cube ? (size_t)QP * n : 0) : best_cube ? cu.d_x[bi] : hr.d_x[bi];
+        if (best_comp) cc.installed++;
         if ((rc = tree_d2h(t, t->best_x.data(), from + (size_t)best * n, (size_t)n * 8))) return rc;
         t->have_x = true;
         // (the point is a closed leaf of value obj: without it no closed leaf holds the incumbent's value, and the
@@ -3503,6 +3630,17 @@ void mipx_tree_destroy(mipx_tree *t) {
         }
     }
     {
+        CompState &cc = t->cc;
+        if (cc.d_ws) (void)hipFree(cc.d_ws);
+        for (int k = 0; k < 3; k++) {
+            if (cc.d_x[k]) (void)hipFree(cc.d_x[k]);
+            if (cc.d_out[k]) (void)hipFree(cc.d_out[k]);
+            if (cc.h_out[k]) (void)hipHostFree(cc.h_out[k]);
+            if (cc.e0[k]) (void)hipEventDestroy(cc.e0[k]);
+            if (cc.e1[k]) (void)hipEventDestroy(cc.e1[k]);
+        }
+    }
+    {
         RcState &rs = t->rc;
         for (int k = 0; k < 3; k++) {
             if (rs.d_y[k]) (void)hipFree(rs.d_y[k]);
@@ -4338,4 +4476,5 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "fixprop_api.hip.h"
 #include "wrepair_api.hip.h"
 #include "cube_api.hip.h"
+#include "complete_api.hip.h"
 #include "objstep_api.hip.h"
