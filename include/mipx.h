@@ -543,5 +543,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_wrepair.h" /* weighted row repair behind the primal heuristic on the GPU */
 #include "mipx_cube.h" /* cube search beside the primal heuristic on the GPU */
 #include "mipx_complete.h" /* heuristic points completed over the continuous columns by a batched LP */
+#include "mipx_finish.h" /* test scaffolding: the device finish of a frontier step on a caller's data */
 
 #endif /* MIPX_H */

@@ -388,6 +388,22 @@ COMPLETE_STATUS = {0: 'completed', 1: 'infeasible', 2: 'limit', 3: 'skipped', 4:
 # the tolerance a completed point is checked with, in the engine and by default in complete_batch
 DEFAULT_COMPLETION_TOL = 1e-6
 
+# ... and those of include/mipx_finish.h (test scaffolding: the device finish of a frontier step on a caller's data),
+# which mipx.h includes (tests/test_finish_abi.py checks them against that header)
+_FINISH_SIGNATURES = {
+    'mipx_finish_step_batch': (_i, [_vp] + [_i] * 7 + [_vp] * 7 + [_i] + [_vp] * 14),
+    'mipx_pc_apply_batch': (_i, [_vp, _i, _i] + [_vp] * 7),
+}
+FINISH_SYMBOLS = list(_FINISH_SIGNATURES)
+# the records of csrc/finish_records.h (tests/support/finish_layout_check.cpp checks the offsets against the structs)
+OPEN_ENTRY_DTYPE = np.dtype([('key', '<f8'), ('bval', '<f8'), ('slot', '<i4'), ('depth', '<i4'), ('bidx_dir', '<i4'),
+                             ('anchor', '<i4')])
+PC_SAMPLE_DTYPE = np.dtype([('var_dir', '<i4'), ('status', '<i4'), ('obj', '<f8'), ('bound', '<f8'), ('vc', '<f8')])
+FINISH_SUMMARY_DTYPE = np.dtype([('host_path', '<i4'), ('n_open', '<i4'), ('n_dead', '<i4'), ('n_samples', '<i4'),
+                                 ('unbounded', '<i4'), ('incumbent_pos', '<i4'), ('n_deferred', '<i4'), ('pad0', '<i4'),
+                                 ('evaluated', '<i8'), ('dives', '<i8'), ('pivots', '<i8'), ('closed_min', '<f8'),
+                                 ('primal', '<f8'), ('primal_before', '<f8'), ('pad', '<i8', (6,))])
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -407,7 +423,8 @@ def lib():
                                       list(_PROP_SIGNATURES.items()) + list(_RCFIX_SIGNATURES.items()) +
                                       list(_LSEARCH_SIGNATURES.items()) + list(_OBJSTEP_SIGNATURES.items()) +
                                       list(_FIXPROP_SIGNATURES.items()) + list(_WREPAIR_SIGNATURES.items()) +
-                                      list(_CUBE_SIGNATURES.items()) + list(_COMPLETE_SIGNATURES.items())):
+                                      list(_CUBE_SIGNATURES.items()) + list(_COMPLETE_SIGNATURES.items()) +
+                                      list(_FINISH_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -710,6 +727,58 @@ def branch_score_batch_dev(ctx, n, B, n_int, d_int_idx, d_x, d_status, rule, d_c
     rc = lib().mipx_branch_score_batch_dev(ctx._h, int(n), int(B), int(n_int), d_int_idx, d_x, d_status, int(rule),
                                            d_cost_l, d_cost_r, d_has_entry, d_branch_idx, d_mip_feasible, d_n_unprobed)
     ctx.check(rc, 'mipx_branch_score_batch_dev')
+
+
+def finish_step_batch(ctx, step, fill=0x5a):
+    """Test scaffolding (mipx_finish_step_batch, include/mipx_finish.h): the device finish on one synthetic step.
+    step: a mapping with the scalars n, m, B, dive, rule, ask_count, ask_cap, primal; the K1 / K4 outputs status, bidx,
+    mipf, nprobe, npiv, dvar, ddir, obj, bval, dval ((dive + 1) * B each); vout, slot, par_i, par_d, budget; the pool
+    pool_l, pool_u, pool_v; with rule 1 the table cost_l, cost_r, has, times, own.  Nothing of step is written.
+    Returns dict of summary (one FINISH_SUMMARY_DTYPE record), open, dead, samples, sample_keys (whole arrays, every
+    byte `fill` where the kernels wrote nothing), pool_l, pool_u, pool_v, primal and the five table arrays."""
+    n, m, B, dive, rule = (int(step[k]) for k in ('n', 'm', 'B', 'dive', 'rule'))
+    P, per, nv = (dive + 1) * B, 2 * (1 + dive), n + m
+    out_i = np.concatenate([_arr(step[k], np.int32, P) for k in ('status', 'bidx', 'mipf', 'nprobe', 'npiv', 'dvar', 'ddir')])
+    out_d = np.concatenate([_arr(step[k], np.float64, P) for k in ('obj', 'bval', 'dval')])
+    vout, slot = _arr(step['vout'], np.int8, (P, nv)), _arr(step['slot'], np.int32, B)
+    par_i, par_d = _arr(step['par_i'], np.int32, (4, B)), _arr(step['par_d'], np.float64, (2, B))
+    budget = _arr(step['budget'], np.int32, (B, per))
+    pool_l, pool_u = (np.array(step[k], dtype=np.float64, order='C').reshape(-1, n) for k in ('pool_l', 'pool_u'))
+    pool_v = np.array(step['pool_v'], dtype=np.int8, order='C').reshape(-1, nv)
+    rows = pool_l.shape[0]
+    assert pool_u.shape[0] == rows and pool_v.shape[0] == rows
+    primal = np.array([step['primal']], np.float64)
+    tab = [None] * 5
+    if rule == 1:
+        tab = [np.array(step[k], dtype=dt, order='C').reshape(sz) for k, dt, sz in
+               (('cost_l', np.float64, n), ('cost_r', np.float64, n), ('has', np.uint8, n), ('times', np.int32, 2 * n),
+                ('own', np.float64, 4 * n))]
+    summary = np.full(FINISH_SUMMARY_DTYPE.itemsize, fill, np.uint8).view(FINISH_SUMMARY_DTYPE)
+    open_ = np.full(per * B * OPEN_ENTRY_DTYPE.itemsize, fill, np.uint8).view(OPEN_ENTRY_DTYPE)
+    dead = np.full(per * B * 4, fill, np.uint8).view(np.int32)
+    samples = np.full(P * PC_SAMPLE_DTYPE.itemsize, fill, np.uint8).view(PC_SAMPLE_DTYPE)
+    keys = np.full(P * 4, fill, np.uint8).view(np.int32)
+    rc = lib().mipx_finish_step_batch(ctx._h, n, m, B, dive, rule, int(step['ask_count']), int(step['ask_cap']), _ptr(out_i),
+                                      _ptr(out_d), _ptr(vout), _ptr(slot), _ptr(par_i), _ptr(par_d), _ptr(budget), rows,
+                                      _ptr(pool_l), _ptr(pool_u), _ptr(pool_v), _ptr(primal), *(_ptr(a) for a in tab),
+                                      _ptr(summary), _ptr(open_), _ptr(dead), _ptr(samples) if rule == 1 else None,
+                                      _ptr(keys) if rule == 1 else None)
+    ctx.check(rc, 'mipx_finish_step_batch')
+    return dict(summary=summary[0], open=open_, dead=dead, samples=samples, sample_keys=keys, pool_l=pool_l, pool_u=pool_u,
+                pool_v=pool_v, primal=primal[0], cost_l=tab[0], cost_r=tab[1], has=tab[2], times=tab[3], own=tab[4])
+
+
+def pc_apply_batch(ctx, n, samples, cost_l, cost_r, has, times, own):
+    """Test scaffolding (mipx_pc_apply_batch): the pseudo-cost recurrence on host-sent samples (PC_SAMPLE_DTYPE records,
+    in list order).  Returns the table after them as (cost_l, cost_r, has, times, own); the inputs are not written."""
+    samples = np.ascontiguousarray(samples, dtype=PC_SAMPLE_DTYPE).reshape(-1)
+    keys = np.ascontiguousarray(samples['var_dir'], dtype=np.int32)
+    tab = [np.array(a, dtype=dt, order='C').reshape(sz) for a, dt, sz in
+           ((cost_l, np.float64, n), (cost_r, np.float64, n), (has, np.uint8, n), (times, np.int32, 2 * n), (own, np.float64, 4 * n))]
+    rc = lib().mipx_pc_apply_batch(ctx._h, int(n), len(samples), _ptr(samples) if len(samples) else None,
+                                   _ptr(keys) if len(samples) else None, *(_ptr(a) for a in tab))
+    ctx.check(rc, 'mipx_pc_apply_batch')
+    return tuple(tab)
 
 
 def solve_multi(ctx, A, b, c, l, u, max_iter=0):

@@ -26,39 +26,19 @@
 // kernels see the counter and do nothing.
 // Pool rows for the children are handed out by the host BEFORE the launch (chain k, level p,
 // direction d owns budget[k][2 p + d]): no device allocator, the same rows in every run.
+// The free rows come back in budget order: chain by chain, level by level, left then right, every row of the
+// chain's budget that holds no open node (a level that did not branch returns both rows, a level that dived returns
+// the row of the child solved in place, a chain left to the host returns all of them).
+// Input contract: LP values do not decrease down a chain (obj[pos + B] >= obj[pos] wherever the child counts), as
+// the values of K1's plunge do; finish_candidates relies on it (below).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "finish_records.h"   // OpenEntry, PcSample, FinishSummary
 #include "lp_kernel.hip.h"
 
 namespace mipx {
-
-struct OpenEntry {       // one new open node, as the host's queue and node table need it
-    double key;          // its inherited bound (the parent's LP objective)
-    double bval;
-    int32_t slot, depth, bidx_dir, anchor;   // bidx_dir = 2 * branching variable + direction
-};
-static_assert(sizeof(OpenEntry) == 32, "OpenEntry layout");
-
-struct PcSample {        // one pseudo-cost update (pseudo_cost.py:68-100), in the order they are applied
-    int32_t var_dir;     // 2 * variable + direction (0 left, 1 right)
-    int32_t status;      // LP status of the child the sample comes from
-    double obj, bound, vc;   // its objective, its parent's bound, the variable change
-};
-static_assert(sizeof(PcSample) == 32, "PcSample layout");
-
-struct FinishSummary {
-    int32_t host_path;           // 1: probe requests were filed -- the host path finishes the step
-    int32_t n_open, n_dead, n_samples;
-    int32_t unbounded, incumbent_pos;   // output position of the step's best improving integral node, -1: none
-    int32_t n_deferred, pad0;           // nodes that filed probe requests: left to the host, after everything else
-    int64_t evaluated, dives, pivots;
-    double closed_min, primal;   // lowest value among the step's closed leaves; the incumbent value after the step
-    double primal_before;        // ... and before it: what the step's decisions compared against
-    int64_t pad[6];
-};
-static_assert(sizeof(FinishSummary) == 128, "FinishSummary layout");
 
 struct FinishArgs {
     int n, m, B, dive, rule;

@@ -1481,6 +1481,24 @@ void pc_update(mipx_tree *t, int var, int dir, int lp_status, double objective, 
     }
 }
 
+// A filled FinishArgs -- and with pseudo costs (g.rule == 1) the table version the step's samples go to -- as
+// launches on st: the one place the finish kernels are launched from (launch_finish below, and
+// mipx_finish_step_batch of finish_api.hip.h on caller data).
+void enqueue_finish(const mipx::FinishArgs &g, const mipx::PcApplyArgs *a, hipStream_t st) {
+    const int B = g.B;
+    hipLaunchKernelGGL(mipx::finish_candidates, dim3((B + 255) / 256), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(mipx::finish_prefix_min, dim3(1), dim3(1024), 0, st, g);
+    hipLaunchKernelGGL(mipx::finish_decide, dim3((B + 255) / 256), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(mipx::finish_scan, dim3(1), dim3(1024), 0, st, g);
+    if (g.n <= 256) hipLaunchKernelGGL((mipx::finish_write<1>), dim3(B), dim3(256), 0, st, g);
+    else if (g.n <= 512) hipLaunchKernelGGL((mipx::finish_write<2>), dim3(B), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((mipx::finish_write<4>), dim3(B), dim3(256), 0, st, g);
+    if (g.rule == 1) {
+        hipLaunchKernelGGL(mipx::finish_samples, dim3((B + 255) / 256), dim3(256), 0, st, g);
+        hipLaunchKernelGGL(mipx::pc_apply, dim3(2 * g.n), dim3(64), 0, st, *a);
+    }
+}
+
 // the kernels that finish a step on the device, queued behind its scoring
 int launch_finish(mipx_tree *t, StepBuf &S) {
     mipx_ctx *ctx = t->ctx;
@@ -1505,21 +1523,13 @@ int launch_finish(mipx_tree *t, StepBuf &S) {
     g.c_info = S.c_info; g.c_cnt = S.c_cnt; g.c_eval = S.c_eval; g.c_val = S.c_val; g.c_flag = S.c_flag;
     g.sum = S.d_sum; g.open = S.d_open; g.dead = S.d_dead; g.samples = S.d_samples; g.sample_keys = S.d_skeys;
     g.c_run = S.c_val + 2 * MB;
-    hipLaunchKernelGGL(mipx::finish_candidates, dim3((B + 255) / 256), dim3(256), 0, st, g);
-    hipLaunchKernelGGL(mipx::finish_prefix_min, dim3(1), dim3(1024), 0, st, g);
-    hipLaunchKernelGGL(mipx::finish_decide, dim3((B + 255) / 256), dim3(256), 0, st, g);
-    hipLaunchKernelGGL(mipx::finish_scan, dim3(1), dim3(1024), 0, st, g);
-    if (t->n <= 256) hipLaunchKernelGGL((mipx::finish_write<1>), dim3(B), dim3(256), 0, st, g);
-    else if (t->n <= 512) hipLaunchKernelGGL((mipx::finish_write<2>), dim3(B), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((mipx::finish_write<4>), dim3(B), dim3(256), 0, st, g);
+    mipx::PcApplyArgs a;
     if (t->rule == 1) {
-        hipLaunchKernelGGL(mipx::finish_samples, dim3((B + 255) / 256), dim3(256), 0, st, g);
-        mipx::PcApplyArgs a;
         const TabPtr tb = tab_at(t, S.tabv);
         a.n = t->n; a.sum = S.d_sum; a.count = -1; a.samples = S.d_samples; a.keys = S.d_skeys;
         a.cost_l = tb.cl; a.cost_r = tb.cr; a.has = tb.has; a.times = tb.times; a.own = tb.own;
-        hipLaunchKernelGGL(mipx::pc_apply, dim3(2 * t->n), dim3(64), 0, st, a);
     }
+    enqueue_finish(g, t->rule == 1 ? &a : nullptr, st);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(S.done, st));
     return MIPX_OK;
@@ -4478,3 +4488,4 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "cube_api.hip.h"
 #include "complete_api.hip.h"
 #include "objstep_api.hip.h"
+#include "finish_api.hip.h"

@@ -480,18 +480,26 @@ def test_example_models_batched_mode_with_defaults(Node):
     (64, 32, 64, 4, 'most fractional', 'best first', 25),
     (40, 16, 16, 3, 'pseudo cost', 'depth first', 60),
     (256, 128, 512, 8, 'pseudo cost', 'best first', 40),
-    (300, 150, 64, 4, 'pseudo cost', 'best first', 40)])    # (the HBM-streaming kernel)
+    (300, 150, 64, 4, 'pseudo cost', 'best first', 40),    # (the HBM-streaming kernel)
+    # beyond 1024 chains: the one-workgroup kernels of the finish give a thread several chains.  Seed 1 as every row;
+    # on this instance the device finishes steps that start with 12239, 2761 and 1735 open nodes (the first row), and
+    # six steps of 6762 to 9281 open nodes, 1536 chains each (the second); either search ends within the 24 steps
+    (64, 32, 4096, 1, 'pseudo cost', 'best first', 24),
+    (64, 32, 1536, 8, 'pseudo cost', 'best first', 24)])
 def test_device_finish_matches_the_host_loop(n, m, B, dive, rule, search, steps):
     """The device finish (csrc/finish_kernels.hip.h: decisions, child records, compact open list, free
     rows, pseudo-cost recurrence as kernels) against the host loop it replaces (MIPX_HOST_FINISH=1: the
     restatement of branch_and_bound.py:243-266 / pseudo_cost.py:68-100 this engine was pinned with), one
     step per call so that both see the same table at every launch: after every step the same counters,
     bounds, open-node count and -- bit for bit -- the same pseudo-cost table; at the end the same open
-    nodes (bounds, bases, inherited bounds)."""
+    nodes (bounds, bases, inherited bounds).  The rows with B > 1024 must also see three device-finished steps of 1025
+    chains and more: steps in which a thread of finish_prefix_min / finish_scan owns several chains."""
     from simple_mip_solver_amd import _ffi
     ctx = _ffi.default_context()
     A, b, c, l, u, ints = random_dense_milp_arrays(n, m, seed=1)
     probs = []
+    # the pool: a wide row needs several steps' budget of B 2 (1 + dive) rows beside its open nodes
+    pool = 1 << 15 if B <= 1024 else 8 * B * 2 * (1 + dive)
 
     def make(host):
         old = os.environ.pop('MIPX_HOST_FINISH', None)
@@ -499,7 +507,7 @@ def test_device_finish_matches_the_host_loop(n, m, B, dive, rule, search, steps)
             os.environ['MIPX_HOST_FINISH'] = '1'
         probs.append(_ffi.Problem(ctx, A, b, c))     # (a problem of its own: the root's anchor belongs to the problem)
         try:
-            t = _ffi.Tree(probs[-1], ints, l, u, branch_rule=rule, search_rule=search, max_batch=B, pool_capacity=1 << 15)
+            t = _ffi.Tree(probs[-1], ints, l, u, branch_rule=rule, search_rule=search, max_batch=B, pool_capacity=pool)
         finally:
             os.environ.pop('MIPX_HOST_FINISH', None)
             if old is not None:
@@ -511,6 +519,7 @@ def test_device_finish_matches_the_host_loop(n, m, B, dive, rule, search, steps)
     keys = ('evaluated_nodes', 'lp_solved', 'probes_solved', 'pivots', 'open_nodes', 'steps', 'dives', 'dual_bound',
             'primal_bound', 'status')
     fast_steps, prev = 0, 0
+    wide_steps, open_before = 0, 1     # device-finished steps of 1025 chains and more
     for step in range(steps):
         a = dev.solve(mip_gap=1e-4, frontier_batch=B, max_steps=1)
         h = host.solve(mip_gap=1e-4, frontier_batch=B, max_steps=1)
@@ -519,10 +528,13 @@ def test_device_finish_matches_the_host_loop(n, m, B, dive, rule, search, steps)
         for x, y in zip(pa, ph):
             assert np.array_equal(x, y), step
         fast_steps += a['probes_solved'] == prev    # (no probe request in the step: the device finished it)
-        prev = a['probes_solved']
+        wide_steps += a['probes_solved'] == prev and open_before >= 1025
+        prev, open_before = a['probes_solved'], a['open_nodes']
         if a['status'] != 4:
             break
     assert fast_steps > 0      # steps without probe requests did go through the device finish
+    if B > 1024:
+        assert wide_steps >= 3, wide_steps     # ... of which these ran with two chains and more per scan thread
     N = a['open_nodes']
     if N:
         key = lambda r: sorted((r[3][k], r[0][k].tobytes(), r[1][k].tobytes(), r[2][k].tobytes()) for k in range(len(r[3])))
