@@ -543,6 +543,7 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_wrepair.h" /* weighted row repair behind the primal heuristic on the GPU */
 #include "mipx_cube.h" /* cube search beside the primal heuristic on the GPU */
 #include "mipx_complete.h" /* heuristic points completed over the continuous columns by a batched LP */
+#include "mipx_lpdive.h" /* LP diving: fix a column, re-solve the batch of LPs, repeat */
 #include "mipx_finish.h" /* test scaffolding: the device finish of a frontier step on a caller's data */
 
 #endif /* MIPX_H */

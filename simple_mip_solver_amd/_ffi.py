@@ -388,6 +388,20 @@ COMPLETE_STATUS = {0: 'completed', 1: 'infeasible', 2: 'limit', 3: 'skipped', 4:
 # the tolerance a completed point is checked with, in the engine and by default in complete_batch
 DEFAULT_COMPLETION_TOL = 1e-6
 
+# ... and those of include/mipx_lpdive.h (LP diving: fix a column, re-solve the batch, repeat), which mipx.h includes
+# (tests/test_lp_dive_abi.py checks them against that header)
+_LPDIVE_SIGNATURES = {
+    'mipx_lpdive_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _vp, _vp, _d, _i, _i] + [_vp] * 7),
+    'mipx_tree_set_lpdive': (_i, [_vp, _i, _i, _i]),
+    'mipx_tree_lpdive_stats': (_i, [_vp, _vp]),
+}
+LPDIVE_SYMBOLS = list(_LPDIVE_SIGNATURES)
+LPDIVE_STATS_KEYS = ('points', 'feasible', 'infeasible', 'failed', 'moves', 'incumbents', 'pivots', 'kernel_us')
+LPDIVE_STATUS = {0: 'feasible', 1: 'infeasible', 2: 'limit', 3: 'skipped', 4: 'rejected', 5: 'cutoff'}
+LPDIVE_RULES = {'fractional': 0, 'coefficient': 1}
+DEFAULT_LP_DIVE_ROUNDS = 64
+MAX_LP_DIVE_ROUNDS = 1024
+
 # ... and those of include/mipx_finish.h (test scaffolding: the device finish of a frontier step on a caller's data),
 # which mipx.h includes (tests/test_finish_abi.py checks them against that header)
 _FINISH_SIGNATURES = {
@@ -424,7 +438,7 @@ def lib():
                                       list(_LSEARCH_SIGNATURES.items()) + list(_OBJSTEP_SIGNATURES.items()) +
                                       list(_FIXPROP_SIGNATURES.items()) + list(_WREPAIR_SIGNATURES.items()) +
                                       list(_CUBE_SIGNATURES.items()) + list(_COMPLETE_SIGNATURES.items()) +
-                                      list(_FINISH_SIGNATURES.items())):
+                                      list(_LPDIVE_SIGNATURES.items()) + list(_FINISH_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -1034,6 +1048,28 @@ class Problem:
         self.ctx.check(rc, 'mipx_complete_batch')
         return dict(x=xo, obj=obj, status=status, pivots=pivots)
 
+    def lpdive_batch(self, x, l, u, integer_indices, vstat=None, skip=None, cutoff=np.inf, max_rounds=DEFAULT_LP_DIVE_ROUNDS,
+                     rule=0):
+        """LP dives on host buffers (mipx_lpdive_batch, include/mipx_lpdive.h): x (batch, n) LP points, l, u (batch, n)
+        the boxes they are optimal over, vstat None or (batch, n + m) basis codes of those LPs, skip an optional
+        (batch,) mask, rule 0 (fractional) or 1 (coefficient).  Returns dict of x (batch, n), obj, status (LPDIVE_STATUS
+        codes), rounds, fixings, flips and pivots."""
+        n = self.n
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n)
+        B = x.shape[0]
+        l = np.ascontiguousarray(l, dtype=np.float64).reshape(B, n)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(B, n)
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        vs = None if vstat is None else np.ascontiguousarray(vstat, dtype=np.int8).reshape(B, n + self.m)
+        sk = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8).reshape(B)
+        xo = np.zeros((B, n)); obj = np.zeros(B)
+        status, rounds, fixings, flips, pivots = (np.zeros(B, np.int32) for _ in range(5))
+        rc = lib().mipx_lpdive_batch(self._h, B, _ptr(x), _ptr(l), _ptr(u), _ptr(ii), len(ii), _ptr(vs), _ptr(sk), float(cutoff),
+                                     int(max_rounds), int(rule), _ptr(xo), _ptr(obj), _ptr(status), _ptr(rounds), _ptr(fixings),
+                                     _ptr(flips), _ptr(pivots))
+        self.ctx.check(rc, 'mipx_lpdive_batch')
+        return dict(x=xo, obj=obj, status=status, rounds=rounds, fixings=fixings, flips=flips, pivots=pivots)
+
     def propagate_batch(self, l, u, integer_indices, cutoff=None, tol=PROPAGATION_TOL, max_rounds=DEFAULT_PROPAGATION_ROUNDS):
         """Bound propagation on host buffers (mipx_propagate_batch, include/mipx_prop.h): l, u (batch, n) boxes,
         cutoff None or an objective value no point above which is of interest.  Returns dict of l, u (batch, n),
@@ -1522,6 +1558,17 @@ class Tree:
         out = np.zeros(8, np.int64)
         self.problem.ctx.check(lib().mipx_tree_completion_stats(self._h, _ptr(out)), 'mipx_tree_completion_stats')
         return dict(zip(COMPLETE_STATS_KEYS, (int(v) for v in out)))
+
+    def set_lpdive(self, max_rounds=DEFAULT_LP_DIVE_ROUNDS, every=0, rule=0):
+        """LP dives on the LP points of a step's first nodes while the search holds no incumbent, or every `every` steps
+        (mipx_tree_set_lpdive, include/mipx_lpdive.h; max_rounds 0: off).  After set_heuristic."""
+        self.problem.ctx.check(lib().mipx_tree_set_lpdive(self._h, int(max_rounds), int(every), int(rule)), 'mipx_tree_set_lpdive')
+
+    def lpdive_stats(self):
+        """dict(points, feasible, infeasible, failed, moves, incumbents, pivots, kernel_us) (mipx_tree_lpdive_stats)."""
+        out = np.zeros(8, np.int64)
+        self.problem.ctx.check(lib().mipx_tree_lpdive_stats(self._h, _ptr(out)), 'mipx_tree_lpdive_stats')
+        return dict(zip(LPDIVE_STATS_KEYS, (int(v) for v in out)))
 
     def set_objective_step(self, step):
         """Prune at one objective step below the incumbent (mipx_tree_set_objective_step, include/mipx_objstep.h):

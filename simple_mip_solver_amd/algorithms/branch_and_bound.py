@@ -126,7 +126,8 @@ class BranchAndBound(BaseAlgorithm):
                  lp_batch=None, pool_capacity=1 << 16, anchor=None, dive=None, comm=None, exchange_every=5,
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
                  propagate=None, reduced_cost=None, objective_step=None, local_search=None, fix_propagate=None,
-                 weighted_repair=None, cube_search=None, complete_continuous=None, **kwargs):
+                 weighted_repair=None, cube_search=None, complete_continuous=None, lp_dive=None, lp_dive_every=None,
+                 **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -253,7 +254,16 @@ class BranchAndBound(BaseAlgorithm):
         solved on the GPU (include/mipx_complete.h), all points of a step in one launch, warm from the basis of the
         node LP the point came from.  A completed point (every row within 1e-6) takes its source's place in the
         contest for the step's incumbent.  On a model without continuous columns nothing is launched.  Inherited by
-        restart() with primal_heuristic.  Counters: `completion_stats`."""
+        restart() with primal_heuristic.  Counters: `completion_stats`.
+        lp_dive (extension; needs primal_heuristic; default None = off): True (64 rounds) or the round cap 1..1024.
+        An LP dive on the GPU (include/mipx_lpdive.h) from the LP point of each of the step's first nodes, inside that
+        node's bounds: fix one fractional integer column at its rounding, re-solve all the points' LPs in one
+        warm-started launch of the node-LP kernel so that the continuous columns and the other integers adapt, flip
+        the fixing once where the LP turns infeasible, and repeat until every integer column is integral; the point
+        is then completed and checked as complete_continuous does.  It runs in the steps in which the search holds no
+        incumbent, and with lp_dive_every=k (a positive integer; default None) in every k-th step as well.  A feasible
+        point competes for the step's incumbent behind the other families.  Inherited by restart() with
+        primal_heuristic.  Counters: `lp_dive_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -265,7 +275,8 @@ class BranchAndBound(BaseAlgorithm):
                            frontier_batch=frontier_batch, pool_capacity=pool_capacity, anchor=anchor, dive=dive,
                            host_spill=host_spill, tree_record=tree_record, primal_heuristic=primal_heuristic,
                            local_search=local_search, fix_propagate=fix_propagate, weighted_repair=weighted_repair,
-                           cube_search=cube_search, complete_continuous=complete_continuous)
+                           cube_search=cube_search, complete_continuous=complete_continuous, lp_dive=lp_dive,
+                           lp_dive_every=lp_dive_every)
         self._given_kwargs = dict(kwargs)
         self.restart_stats = None
         self.lp_batch = lp_batch
@@ -394,6 +405,19 @@ class BranchAndBound(BaseAlgorithm):
             raise ValueError('complete_continuous needs primal_heuristic (it completes the points the heuristics end on)')
         self._complete_continuous = complete_continuous
         self.completion_stats = None
+        if not (lp_dive is None or lp_dive is True or (isinstance(lp_dive, int) and not isinstance(lp_dive, bool) and
+                                                        1 <= lp_dive <= 1024)):
+            raise ValueError('lp_dive is None, True or a round cap from 1 to 1024')
+        if not (lp_dive_every is None or (isinstance(lp_dive_every, int) and not isinstance(lp_dive_every, bool) and
+                                          lp_dive_every > 0)):
+            raise ValueError('lp_dive_every is None or a positive integer')
+        if lp_dive is not None and primal_heuristic is None:
+            raise ValueError('lp_dive needs primal_heuristic (it dives from the LP points the heuristic takes)')
+        if lp_dive_every is not None and lp_dive is None:
+            raise ValueError('lp_dive_every needs lp_dive')
+        self._lp_dive = lp_dive
+        self._lp_dive_every = lp_dive_every
+        self.lp_dive_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -583,6 +607,9 @@ class BranchAndBound(BaseAlgorithm):
                 self._native.set_cube_search(self._cube_search)
             if self._complete_continuous:
                 self._native.set_completion(True)
+            if self._lp_dive:
+                self._native.set_lpdive(64 if self._lp_dive is True else self._lp_dive,
+                                        self._lp_dive_every or 0)
             if self._objective_step:
                 self._native.set_objective_step(self._objective_step)
             if self._propagate:
@@ -664,6 +691,8 @@ class BranchAndBound(BaseAlgorithm):
             self.cube_search_stats = self._native.cube_search_stats()
         if self._complete_continuous:
             self.completion_stats = self._native.completion_stats()
+        if self._lp_dive:
+            self.lp_dive_stats = self._native.lpdive_stats()
         if self._native.cuts:   # the running GMIC totals bound() threads through the kwargs
             totals = self._native.cut_stats()
             self._native_cuts_dropped = totals.pop('dropped')
@@ -671,7 +700,8 @@ class BranchAndBound(BaseAlgorithm):
                 self._kwargs[key] = self._native_totals0.get(key, 0) + value
 
     _restart_overrides = ('node_limit', 'mip_gap', 'max_run_time', 'frontier_batch', 'anchor', 'dive', 'primal_heuristic',
-                          'local_search', 'fix_propagate', 'weighted_repair', 'cube_search', 'complete_continuous')
+                          'local_search', 'fix_propagate', 'weighted_repair', 'cube_search', 'complete_continuous', 'lp_dive',
+                          'lp_dive_every')
 
     def restart(self, b, **overrides):
         """A new, unsolved BranchAndBound for the same A, c, bounds and integer indices at the right-hand side
@@ -682,8 +712,9 @@ class BranchAndBound(BaseAlgorithm):
         find_parameterized_dual_bound (a CyLPArray of the constraint's shape, negated with the same warning if
         the constraints were flipped at instantiation).  Same Node class and keyword options; overrides may
         change node_limit, mip_gap, max_run_time, frontier_batch (at most this search's), anchor, dive,
-        primal_heuristic, local_search, fix_propagate, weighted_repair, cube_search and complete_continuous (the last
-        five run on the heuristic's points: an override that turns primal_heuristic off turns the inherited ones off with it).
+        primal_heuristic, local_search, fix_propagate, weighted_repair, cube_search, complete_continuous and lp_dive
+        with lp_dive_every (all but the first run on the heuristic's points: an override that turns primal_heuristic
+        off turns the inherited ones off with it).
         Needs frontier_batch and tree_record=True and a solve() before; not with comm; the restarted search
         records no dual function.  `restart_stats` of the new search reports the seeding."""
         assert self.frontier_batch is not None and self._tree_record, \
@@ -710,6 +741,10 @@ class BranchAndBound(BaseAlgorithm):
             opts['cube_search'] = None   # (and the cube search)
         if not opts.get('primal_heuristic') and 'complete_continuous' not in overrides:
             opts['complete_continuous'] = None   # (and the completion)
+        if not opts.get('primal_heuristic') and 'lp_dive' not in overrides:
+            opts['lp_dive'] = None   # (and the LP dive)
+        if not opts.get('lp_dive') and 'lp_dive_every' not in overrides:
+            opts['lp_dive_every'] = None
         assert isinstance(opts['frontier_batch'], int) and 0 < opts['frontier_batch'] <= self.frontier_batch, \
             'a restarted search steps with at most the frontier_batch of its source'
         if self._swapped_constraint_direction:
@@ -756,6 +791,9 @@ class BranchAndBound(BaseAlgorithm):
             self._native.set_cube_search(self._cube_search)
         if self._complete_continuous:
             self._native.set_completion(True)
+        if self._lp_dive:
+            self._native.set_lpdive(64 if self._lp_dive is True else self._lp_dive,
+                                    self._lp_dive_every or 0)
         self.restart_stats = self._native.restart_stats()
         self._kwargs['next_node_idx'] = source._kwargs['next_node_idx']
 

@@ -88,10 +88,48 @@ __global__ void __launch_bounds__(kCompNT) complete_prepare(CompArgs a) {
     if (tid == 0) a.ws_skipped[g] = bad;
 }
 
+// FINISH of include/mipx_complete.h for one point, by the kCompNT threads of a workgroup (xt, isint: kCompMax entries
+// of LDS each): x^ is xl with the integer columns taken from `fixed`; l, u are the bounds the other columns are held
+// to.  Returns whether the point fails (uniform); a point that holds is written to xo (which may be xl) and thread 0
+// returns its objective in *obj (0 for one that fails).  Shared with lpdive_finish (lpdive_kernels.hip.h).
+__device__ __forceinline__ int complete_finish_point(int m, int n, int n_int, double ctol, const double *A, const double *b,
+                                                     const double *c, const double *l, const double *u, const int32_t *int_idx,
+                                                     const double *xl, const double *fixed, double *xo, double *obj,
+                                                     double *xt, uint8_t *isint) {
+    const int tid = threadIdx.x;
+    for (int j = tid; j < n; j += kCompNT) { xt[j] = xl[j]; isint[j] = 0; }
+    __syncthreads();
+    for (int k = tid; k < n_int; k += kCompNT) {
+        const int j = int_idx[k];
+        xt[j] = fixed[j];   // (x~_j, to the bit)
+        isint[j] = 1;
+    }
+    __syncthreads();
+    int bad = 0;
+    for (int i = tid; i < m; i += kCompNT) {
+        const double *row = A + (size_t)i * n;
+        double acc = 0.0;
+        for (int j = 0; j < n; j++) acc += row[j] * xt[j];
+        if (!(acc - b[i] >= -ctol)) bad = 1;
+    }
+    for (int j = tid; j < n; j += kCompNT)
+        if (!isint[j] && !(xt[j] >= l[j] - ctol && xt[j] <= u[j] + ctol)) bad = 1;
+    bad = __syncthreads_or(bad);
+    if (!bad)
+        for (int j = tid; j < n; j += kCompNT) xo[j] = xt[j];
+    if (tid == 0) {
+        double v = 0.0;
+        if (!bad)
+            for (int j = 0; j < n; j++) v += c[j] * xt[j];
+        *obj = v;
+    }
+    return bad;
+}
+
 __global__ void __launch_bounds__(kCompNT) complete_finish(CompArgs a) {
     __shared__ double xt[kCompMax];
     __shared__ uint8_t isint[kCompMax];
-    const int tid = threadIdx.x, m = a.m, n = a.n;
+    const int tid = threadIdx.x, n = a.n;
     const size_t g = (size_t)a.p0 + (size_t)blockIdx.x;
     const int lp = a.ws_lp_status[g];
     int status = a.ws_skipped[g] ? 3 : lp == 0 ? 0 : lp == 1 ? 1 : 2;   // (uniform over the workgroup)
@@ -103,34 +141,10 @@ __global__ void __launch_bounds__(kCompNT) complete_finish(CompArgs a) {
         }
         return;   // (x_out holds x~ since complete_prepare)
     }
-    const double ctol = a.ctol;
-    const double *xl = a.ws_x + g * n, *L = a.ws_L + g * n;
-    for (int j = tid; j < n; j += kCompNT) { xt[j] = xl[j]; isint[j] = 0; }
-    __syncthreads();
-    for (int k = tid; k < a.n_int; k += kCompNT) {
-        const int j = a.int_idx[k];
-        xt[j] = L[j];   // (x~_j, to the bit)
-        isint[j] = 1;
-    }
-    __syncthreads();
-    int bad = 0;
-    for (int i = tid; i < m; i += kCompNT) {
-        const double *row = a.A + (size_t)i * n;
-        double acc = 0.0;
-        for (int j = 0; j < n; j++) acc += row[j] * xt[j];
-        if (!(acc - a.b[i] >= -ctol)) bad = 1;
-    }
-    for (int j = tid; j < n; j += kCompNT)
-        if (!isint[j] && !(xt[j] >= a.l[j] - ctol && xt[j] <= a.u[j] + ctol)) bad = 1;
-    bad = __syncthreads_or(bad);
-    if (!bad) {
-        double *xo = a.x_out + g * n;
-        for (int j = tid; j < n; j += kCompNT) xo[j] = xt[j];
-    }
+    double obj = 0.0;
+    const int bad = complete_finish_point(a.m, n, a.n_int, a.ctol, a.A, a.b, a.c, a.l, a.u, a.int_idx, a.ws_x + g * n,
+                                          a.ws_L + g * n, a.x_out + g * n, &obj, xt, isint);
     if (tid == 0) {
-        double obj = 0.0;
-        if (!bad)
-            for (int j = 0; j < n; j++) obj += a.c[j] * xt[j];
         a.obj_out[g] = obj;
         a.status_out[g] = bad ? 4 : 0;
         a.pivots_out[g] = a.ws_pivots[g];

@@ -67,6 +67,8 @@ int mipx_tree_set_heuristic(mipx_tree *t, int points_per_step, int every_steps, 
         return fail(ctx, MIPX_EINVAL, "mipx_tree_set_heuristic: more points than the cube search was set for (mipx_tree_set_cube_search(t, 0) first)");
     if (t->cc.on && P > t->cc.cap)
         return fail(ctx, MIPX_EINVAL, "mipx_tree_set_heuristic: more points than the completion was set for (mipx_tree_set_completion(t, 0) first)");
+    if (t->ld.on && P > t->ld.cap)
+        return fail(ctx, MIPX_EINVAL, "mipx_tree_set_heuristic: more points than the LP dive was set for (mipx_tree_set_lpdive(t, 0, 0, 0) first)");
     if (P > hr.cap) {   // (set again with more points: the step buffers grow; nothing is in flight before the first step)
         for (int k = 0; k < 3; k++) {
             if (hr.d_x[k]) (void)hipFree(hr.d_x[k]);

@@ -29,6 +29,7 @@
 #include "wrepair_kernels.hip.h"
 #include "cube_kernels.hip.h"
 #include "complete_kernels.hip.h"
+#include "lpdive_kernels.hip.h"
 #include "prop_kernels.hip.h"
 #include "rcfix_kernels.hip.h"
 #include "cglp_kernels.hip.h"
@@ -314,6 +315,7 @@ struct StepBuf {
     int cube_n = 0;   // cube search: the points of this step it was launched on beside the heuristic (0: none)
     int comp_n = 0;   // completion: the points per block of this step it was launched on behind the heuristics (0: none)
     bool comp_cube = false;   // ... and whether the cube's block went with the heuristic's
+    int lpdive_n = 0; // LP dive: the points of this step it was launched on (0: none)
     int prop_n = 0;   // bound propagation: the nodes of this step it was launched on (0: none)
     std::vector<int> rc_cnt;          // reduced-cost tightening: the parents it was launched on, per level, not yet
     hipStream_t rc_stream = nullptr;  // collected (empty: none), and the stream the launches went to
@@ -468,6 +470,22 @@ struct CompState {
     hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
     int64_t tried = 0, completed = 0, infeasible = 0, failed = 0, rescued = 0, installed = 0, pivots = 0;
     double us = 0.0;                 // device time of the two kernels and the LP launch between them
+};
+
+// LP dive (include/mipx_lpdive.h): the caps, the lock counts of rule 1 (once per problem), the dive's workspace
+// (mipx::LpdiveWs for cap points; one, the launches are queued on one stream) and, per step buffer, the dive's points
+// and what comes down with each step (mipx::LpdiveOut).  Nothing of it lies in the packed step buffer.
+struct LpdiveState {
+    bool on = false;
+    int max_rounds = 0, every = 0, rule = 0;
+    int cap = 0;                     // points the buffers are laid out for (the heuristic's cap)
+    int32_t *d_locks = nullptr;
+    char *d_ws = nullptr;
+    double *d_x[3] = {nullptr, nullptr, nullptr};
+    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    int64_t tried = 0, feasible = 0, infeasible = 0, failed = 0, moves = 0, installed = 0, pivots = 0;
+    double us = 0.0;                 // device time of the dive's kernels and the LP launches between them
 };
 
 // Objective step (include/mipx_objstep.h): the step and the counters.
@@ -638,6 +656,7 @@ struct mipx_tree {
     WrState wr;
     CubeState cu;
     CompState cc;
+    LpdiveState ld;
     ObjStepState os;
     PropState pg;
     RcState rc;
@@ -947,6 +966,62 @@ int comp_launch(mipx_problem *p, hipStream_t st, const CompSrc *src, int nsrc, c
     return MIPX_OK;
 }
 
+// One LP dive (include/mipx_lpdive.h) of `batch` points in device memory, queued on `st`: lpdive_prepare, then per
+// round lpdive_step and ONE node-LP launch over all the points, the last lpdive_step and lpdive_finish (d_ws:
+// mipx::LpdiveWs(batch, m, n).bytes() at least; d_locks: lpdive_locks' counts; d_slot: null, or per point the row of
+// d_l0 / d_u0 its box lies in; d_gate: null, or per point the status of its node LP -- a point whose entry is not 0 is
+// skipped; d_x_out is not d_x0).  Every LP launch carries basis codes, as the completion's does.  With `poll` the host
+// reads the round's counter of live points behind every step and stops launching at 0 (the batch entry; the outputs
+// do not depend on it); without, nothing is read.
+int lpdive_launch(mipx_problem *p, hipStream_t st, int batch, const double *d_x0, const double *d_l0, const double *d_u0,
+                  const int32_t *d_slot, const uint8_t *d_skip, const int32_t *d_gate, const int8_t *d_vstat,
+                  const int32_t *d_int_idx, int n_int, const int32_t *d_locks, double cutoff, int max_rounds, int rule,
+                  bool poll, char *d_ws, double *d_x_out, double *d_obj, int32_t *d_status, int32_t *d_rounds,
+                  int32_t *d_fixings, int32_t *d_flips, int32_t *d_pivots) {
+    mipx_ctx *ctx = p->ctx;
+    if (p->m > mipx::kLpdiveMax || p->n > mipx::kLpdiveMax) return fail(ctx, MIPX_ETOOBIG, "LP dive: more than 1024 rows or columns");
+    if (max_rounds < 1 || max_rounds > mipx::kLpdiveMaxRounds) return fail(ctx, MIPX_EINVAL, "LP dive: max_rounds outside 1..1024");
+    if (batch <= 0) return MIPX_OK;
+    const mipx::LpdiveWs w((size_t)batch, (size_t)p->m, (size_t)p->n);
+    mipx::LpdiveArgs a;
+    a.m = p->m; a.n = p->n; a.n_int = n_int; a.rule = rule; a.round = 0; a.max_rounds = max_rounds;
+    a.cutoff = cutoff; a.ftol = 1e-6; a.ctol = 1e-6;
+    a.A = p->dA; a.b = p->db; a.c = p->dc; a.int_idx = d_int_idx; a.locks = d_locks;
+    a.x0 = d_x0; a.l0 = d_l0; a.u0 = d_u0; a.slot = d_slot; a.skip = d_skip; a.gate = d_gate; a.vstat = d_vstat;
+    a.ws_L = (double *)(d_ws + w.L); a.ws_U = (double *)(d_ws + w.U); a.ws_x = (double *)(d_ws + w.x);
+    a.ws_vin = (int8_t *)(d_ws + w.vin); a.ws_vout = (const int8_t *)(d_ws + w.vout);
+    a.ws_lp_obj = (const double *)(d_ws + w.lp_obj); a.ws_lp_status = (const int32_t *)(d_ws + w.lp_status);
+    a.ws_lp_pivots = (const int32_t *)(d_ws + w.lp_pivots); a.ws_rec = (double *)(d_ws + w.rec);
+    a.ws_rec_j = (int32_t *)(d_ws + w.rec_j); a.ws_phase = (int32_t *)(d_ws + w.phase); a.ws_live = (int32_t *)(d_ws + w.live);
+    a.x_out = d_x_out; a.obj_out = d_obj; a.status_out = d_status; a.rounds_out = d_rounds; a.fixings_out = d_fixings;
+    a.flips_out = d_flips; a.pivots_out = d_pivots;
+    HIP_TRY(ctx, hipMemsetAsync(a.ws_live, 0, 4 * (size_t)(mipx::kLpdiveMaxRounds + 2), st));
+    hipLaunchKernelGGL(mipx::lpdive_prepare, dim3((unsigned)batch), dim3(mipx::kLpdiveNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    mipx::LpArgs g = problem_args(p, false);
+    g.l = a.ws_L; g.u = a.ws_U; g.vstat_in = a.ws_vin; g.max_iter = 0;
+    g.status = (int32_t *)(d_ws + w.lp_status); g.obj = (double *)(d_ws + w.lp_obj); g.x = a.ws_x;
+    g.vstat_out = (int8_t *)(d_ws + w.vout); g.npivots = (int32_t *)(d_ws + w.lp_pivots);
+    g.batch = batch;
+    for (a.round = 1; a.round <= max_rounds + 1; a.round++) {
+        hipLaunchKernelGGL(mipx::lpdive_step, dim3((unsigned)batch), dim3(mipx::kLpdiveWave), 0, st, a);
+        HIP_TRY(ctx, hipGetLastError());
+        if (a.round > max_rounds) break;
+        if (poll) {
+            int32_t live = 0;
+            HIP_TRY(ctx, hipMemcpyAsync(&live, a.ws_live + a.round, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            if (live == 0) break;   // (no point goes into this round's LP: every later step would return at once)
+        }
+        mipx::LpArgs h = g;
+        const int rc = launch_lp_any(p, h, batch, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(mipx::lpdive_finish, dim3((unsigned)batch), dim3(mipx::kLpdiveNT), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
 // The step's node LP solutions (level 0, the first positions) through the heuristic, behind its node LPs; the points
 // it did not end feasible on through the fix-and-propagate dive, whose feasible points take their place and go through
 // the heuristic once more (the lift), or through the weighted row repair in the same way (one of the two at most); and
@@ -1059,6 +1134,24 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
         HIP_TRY(ctx, hipEventRecord(cc.e1[bi], st));
         S.comp_n = P;
         S.comp_cube = cu.on;
+    }
+    // LP dive: the LP points again, each inside its node's box (its pool row, as it is when the kernels run: behind the
+    // node LPs of this step and before its finish) and warm from its node LP's final basis; while the host holds no
+    // incumbent, or every ld.every steps
+    S.lpdive_n = 0;
+    LpdiveState &ld = t->ld;
+    if (ld.on && (!(t->primal < std::numeric_limits<double>::infinity()) || (ld.every > 0 && t->steps % ld.every == 0))) {
+        const mipx::LpdiveOut dl((size_t)ld.cap);
+        char *dout = ld.d_out[bi];
+        HIP_TRY(ctx, hipEventRecord(ld.e0[bi], st));
+        const int drc = lpdive_launch(t->prob, st, P, S.d_x, t->pool_l, t->pool_u, S.d_slot, nullptr, S.d.status, S.d_vout,
+                                      t->d_int_idx, t->n_int, ld.d_locks, tree_cutoff(t), ld.max_rounds, ld.rule, false, ld.d_ws,
+                                      ld.d_x[bi], (double *)(dout + dl.obj), (int32_t *)(dout + dl.status),
+                                      (int32_t *)(dout + dl.rounds), (int32_t *)(dout + dl.fixings),
+                                      (int32_t *)(dout + dl.flips), (int32_t *)(dout + dl.pivots));
+        if (drc) return drc;
+        HIP_TRY(ctx, hipEventRecord(ld.e1[bi], st));
+        S.lpdive_n = P;
     }
     return MIPX_OK;
 }
@@ -1250,11 +1343,39 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         const double v = done ? q_obj[QP + k] : cu_obj[k];
         if (best < 0 || v < best_obj) { best = k; best_fp = false; best_cube = true; best_comp = done; best_obj = v; }
     }
+    // LP dive: its counters, and its FEASIBLE points, a family of their own behind every other
+    LpdiveState &ld = t->ld;
+    const int DP = S.lpdive_n;
+    S.lpdive_n = 0;
+    bool best_ld = false;
+    if (DP > 0) {
+        const mipx::LpdiveOut dl((size_t)ld.cap);
+        if ((rc = tree_d2h(t, ld.h_out[bi], ld.d_out[bi], dl.bytes()))) return rc;
+        if (hipEventElapsedTime(&ms, ld.e0[bi], ld.e1[bi]) == hipSuccess) ld.us += 1000.0 * ms;
+        const char *ho = ld.h_out[bi];
+        const double *d_obj = (const double *)(ho + dl.obj);
+        const int32_t *d_status = (const int32_t *)(ho + dl.status), *d_fix = (const int32_t *)(ho + dl.fixings),
+                      *d_flip = (const int32_t *)(ho + dl.flips), *d_piv = (const int32_t *)(ho + dl.pivots);
+        for (int k = 0; k < DP; k++) {
+            if (d_status[k] == MIPX_LPDIVE_SKIPPED) continue;
+            ld.tried++;
+            ld.moves += d_fix[k] + d_flip[k];
+            ld.pivots += d_piv[k];
+            if (d_status[k] == MIPX_LPDIVE_INFEASIBLE || d_status[k] == MIPX_LPDIVE_CUTOFF) ld.infeasible++;
+            else if (d_status[k] != MIPX_LPDIVE_FEASIBLE) ld.failed++;
+            if (d_status[k] != MIPX_LPDIVE_FEASIBLE) continue;
+            ld.feasible++;
+            if (best < 0 || d_obj[k] < best_obj) {
+                best = k; best_fp = false; best_cube = false; best_comp = false; best_ld = true; best_obj = d_obj[k];
+            }
+        }
+    }
     if (best >= 0 && best_obj < t->primal) {
         t->primal = best_obj;
         // (the block that won: a completed point lies in the completion's, at its source's position)
-        const double *from = best_comp ? cc.d_x[bi] + (best_cube ? (size_t)QP * n : 0) : best_cube ? cu.d_x[bi] : hr.d_x[bi];
+        const double *from = best_ld ? ld.d_x[bi] : best_comp ? cc.d_x[bi] + (best_cube ? (size_t)QP * n : 0) : best_cube ? cu.d_x[bi] : hr.d_x[bi];
         if (best_comp) cc.installed++;
+        if (best_ld) ld.installed++;
         if ((rc = tree_d2h(t, t->best_x.data(), from + (size_t)best * n, (size_t)n * 8))) return rc;
         t->have_x = true;
         // (the point is a closed leaf of value obj: without it no closed leaf holds the incumbent's value, and the
@@ -1263,7 +1384,7 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         hr.installed++;
         if (best_fp) (WP > 0 ? wr.installed : fp.installed)++;
         if (best_cube) cu.installed++;
-        const int32_t *lm = best_cube ? cu_ls_moves : best_fp ? fp_ls_moves : ls_moves;
+        const int32_t *lm = best_ld ? nullptr : best_cube ? cu_ls_moves : best_fp ? fp_ls_moves : ls_moves;
         if (lm && lm[2 * best] + lm[2 * best + 1] > 0) ls.installed++;
     }
     return MIPX_OK;
@@ -3651,6 +3772,18 @@ void mipx_tree_destroy(mipx_tree *t) {
         }
     }
     {
+        LpdiveState &ld = t->ld;
+        if (ld.d_ws) (void)hipFree(ld.d_ws);
+        if (ld.d_locks) (void)hipFree(ld.d_locks);
+        for (int k = 0; k < 3; k++) {
+            if (ld.d_x[k]) (void)hipFree(ld.d_x[k]);
+            if (ld.d_out[k]) (void)hipFree(ld.d_out[k]);
+            if (ld.h_out[k]) (void)hipHostFree(ld.h_out[k]);
+            if (ld.e0[k]) (void)hipEventDestroy(ld.e0[k]);
+            if (ld.e1[k]) (void)hipEventDestroy(ld.e1[k]);
+        }
+    }
+    {
         RcState &rs = t->rc;
         for (int k = 0; k < 3; k++) {
             if (rs.d_y[k]) (void)hipFree(rs.d_y[k]);
@@ -4487,5 +4620,6 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "wrepair_api.hip.h"
 #include "cube_api.hip.h"
 #include "complete_api.hip.h"
+#include "lpdive_api.hip.h"
 #include "objstep_api.hip.h"
 #include "finish_api.hip.h"
