@@ -346,7 +346,11 @@ int mipx_tree_create_ex(mipx_problem *p, const int32_t *int_idx, int n_int, cons
  * them (base_node.py:218-226): total_cut_generation_iterations, total_iterations_gmic_created,
  * total_number_gmic_created, total_iterations_gmic_added, total_number_gmic_added,
  * total_iterations_gmic_removed, total_number_gmic_removed; out[7] = cuts dropped for lack of room
- * (a full node list, pool slab or store: 0 unless a capacity was set too small). */
+ * (a full node list, pool slab or store: 0 unless a capacity was set too small).  A cut is dropped once,
+ * for whichever cause; total_number_gmic_created counts every cut K2 made and total_number_gmic_added
+ * every cut the selection took, including those that were then dropped (a selected cut leaves the pool
+ * either way).  A node whose list is full asks the store for nothing; a node that finds the store full
+ * keeps asking for the rest of its selection, so the store's counter can pass store_capacity. */
 int mipx_tree_cut_stats(mipx_tree *t, int64_t out[8]);
 void mipx_tree_destroy(mipx_tree *t);
 /* Run or continue the search (re-entrant like BranchAndBound.solve).  Limits <= 0 mean none.
@@ -545,5 +549,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_complete.h" /* heuristic points completed over the continuous columns by a batched LP */
 #include "mipx_lpdive.h" /* LP diving: fix a column, re-solve the batch of LPs, repeat */
 #include "mipx_finish.h" /* test scaffolding: the device finish of a frontier step on a caller's data */
+#include "mipx_cutround.h" /* test scaffolding: the kernels of a cut round on a caller's data */
 
 #endif /* MIPX_H */

@@ -418,6 +418,16 @@ FINISH_SUMMARY_DTYPE = np.dtype([('host_path', '<i4'), ('n_open', '<i4'), ('n_de
                                  ('evaluated', '<i8'), ('dives', '<i8'), ('pivots', '<i8'), ('closed_min', '<f8'),
                                  ('primal', '<f8'), ('primal_before', '<f8'), ('pad', '<i8', (6,))])
 
+# ... and those of include/mipx_cutround.h (test scaffolding: the kernels of a cut round on a caller's data), which
+# mipx.h includes (tests/test_cut_round_abi.py checks them against that header)
+_CUTROUND_SIGNATURES = {
+    'mipx_cut_round_begin_batch': (_i, [_vp] + [_i] * 6 + [_d] * 2 + [_i] * 3 + [_vp] * 16),
+    'mipx_cut_round_generate_batch': (_i, [_vp] + [_i] * 6 + [_d, _i] + [_d] * 3 + [_vp] * 22),
+}
+CUTROUND_SYMBOLS = list(_CUTROUND_SIGNATURES)
+CUT_FIELDS = ('rounds', 'it_created', 'n_created', 'it_added', 'n_added', 'it_removed', 'n_removed', 'ncut_out', 'stalled',
+              'pool_n', 'slab_n', 'dropped')   # CutField of csrc/tree_kernels.hip.h: the rows of a round's state array
+
 
 def lib():
     """Load libmipx.so; raise MipxError if it has not been built (no fallback)."""
@@ -438,7 +448,8 @@ def lib():
                                       list(_LSEARCH_SIGNATURES.items()) + list(_OBJSTEP_SIGNATURES.items()) +
                                       list(_FIXPROP_SIGNATURES.items()) + list(_WREPAIR_SIGNATURES.items()) +
                                       list(_CUBE_SIGNATURES.items()) + list(_COMPLETE_SIGNATURES.items()) +
-                                      list(_LPDIVE_SIGNATURES.items()) + list(_FINISH_SIGNATURES.items())):
+                                      list(_LPDIVE_SIGNATURES.items()) + list(_FINISH_SIGNATURES.items()) +
+                                      list(_CUTROUND_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -793,6 +804,78 @@ def pc_apply_batch(ctx, n, samples, cost_l, cost_r, has, times, own):
                                    _ptr(keys) if len(samples) else None, *(_ptr(a) for a in tab))
     ctx.check(rc, 'mipx_pc_apply_batch')
     return tuple(tab)
+
+
+def _filled(shape, dtype, fill):
+    """An output array whose every byte is `fill`: what a kernel left alone still holds it."""
+    a = np.empty(shape, dtype)
+    a.view(np.uint8).reshape(-1)[:] = fill
+    return a
+
+
+def cut_round_begin_batch(ctx, rnd, fill=0x5a):
+    """Test scaffolding (mipx_cut_round_begin_batch, include/mipx_cutround.h): cut_gather_state (with rnd['gather']) and
+    cut_round_begin on one synthetic round.  rnd: a mapping with the scalars n, m0, kc, B, round, max_rounds,
+    progress_tol, max_dual_bound, have_dump, gather; status, obj, mipf, y; vstat, ncut, ids, state (12 x B), obj_before,
+    active, counters; with gather slot, pool_ncut, pool_ids.  Nothing of rnd is written.  Returns dict of vstat, ncut, ids,
+    state, obj_before, active, counters (copies, as the kernels left them) and resolve, need_tab (every byte `fill` where
+    the kernels wrote nothing)."""
+    n, m0, kc, B = (int(rnd[k]) for k in ('n', 'm0', 'kc', 'B'))
+    ms = m0 + kc
+    gather = int(rnd['gather'])
+    slot = pool_ncut = pool_ids = None
+    rows = 0
+    if gather:
+        slot, pool_ncut = _arr(rnd['slot'], np.int32, B), _arr(rnd['pool_ncut'], np.int32)
+        rows = len(pool_ncut)
+        pool_ids = _arr(rnd['pool_ids'], np.int32, (rows, kc))
+    status, obj, mipf = _arr(rnd['status'], np.int32, B), _arr(rnd['obj'], np.float64, B), _arr(rnd['mipf'], np.int32, B)
+    y = _arr(rnd['y'], np.float64, (B, ms))
+    out = dict(vstat=np.array(rnd['vstat'], dtype=np.int8, order='C').reshape(B, n + ms),
+               ncut=np.array(rnd['ncut'], dtype=np.int32, order='C').reshape(B),
+               ids=np.array(rnd['ids'], dtype=np.int32, order='C').reshape(B, kc),
+               state=np.array(rnd['state'], dtype=np.int32, order='C').reshape(len(CUT_FIELDS), B),
+               obj_before=np.array(rnd['obj_before'], dtype=np.float64, order='C').reshape(B),
+               active=np.array(rnd['active'], dtype=np.int32, order='C').reshape(B),
+               counters=np.array(rnd['counters'], dtype=np.int32, order='C').reshape(4),
+               resolve=_filled(B, np.int32, fill), need_tab=_filled(B, np.int32, fill))
+    rc = lib().mipx_cut_round_begin_batch(
+        ctx._h, n, m0, kc, B, int(rnd['round']), int(rnd['max_rounds']), float(rnd['progress_tol']), float(rnd['max_dual_bound']),
+        int(rnd['have_dump']), gather, rows, _ptr(slot), _ptr(pool_ncut), _ptr(pool_ids), _ptr(status), _ptr(obj), _ptr(mipf),
+        _ptr(y), *(_ptr(out[k]) for k in ('vstat', 'ncut', 'ids', 'state', 'obj_before', 'active', 'counters', 'resolve', 'need_tab')))
+    ctx.check(rc, 'mipx_cut_round_begin_batch')
+    return out
+
+
+def cut_round_generate_batch(problem, rnd, fill=0x5a):
+    """Test scaffolding (mipx_cut_round_generate_batch): K2 in its slab form, pool_append, K3 over the pool lists and
+    cut_round_apply on one synthetic round of `problem` (its A and b are the shared rows).  rnd: a mapping with the
+    scalars B, kc, slab_rows, chunks, group, store_cap, max_term, max_nonzero_coefs, min_cut_depth, cos_parallel,
+    max_abs_coef; T, idx, x, is_int, active; vstat, ncut, ids, state, pool_list, slab_pi, slab_pi0, store_pi, store_pi0,
+    store_count, resolve, counters.  Nothing of rnd is written.  Returns dict of the in/out arrays as the kernels left them,
+    k2_ncuts, k3_nadded, k3_added, k3_term (every byte `fill` where the kernels wrote nothing) and the chunks and group
+    the launch ran with."""
+    n, m0 = problem.n, problem.m
+    B, kc, SR, cap = (int(rnd[k]) for k in ('B', 'kc', 'slab_rows', 'store_cap'))
+    ms = m0 + kc
+    T, idx = _arr(rnd['T'], np.float64, (B, ms, n)), _arr(rnd['idx'], np.int32, (B, 2 * n + ms))
+    x, is_int, active = _arr(rnd['x'], np.float64, (B, n)), _arr(rnd['is_int'], np.uint8, n), _arr(rnd['active'], np.int32, B)
+    shapes = (('vstat', np.int8, (B, n + ms)), ('ncut', np.int32, (B,)), ('ids', np.int32, (B, kc)),
+              ('state', np.int32, (len(CUT_FIELDS), B)), ('pool_list', np.int32, (B, SR)), ('slab_pi', np.float64, (B, SR, n)),
+              ('slab_pi0', np.float64, (B, SR)), ('store_pi', np.float64, (cap, n)), ('store_pi0', np.float64, (cap,)),
+              ('store_count', np.int32, (1,)), ('resolve', np.int32, (B,)), ('counters', np.int32, (4,)))
+    out = {k: np.array(rnd[k], dtype=dt, order='C').reshape(sh) for k, dt, sh in shapes}
+    out.update(k2_ncuts=_filled(B, np.int32, fill), k3_nadded=_filled(B, np.int32, fill), k3_added=_filled((B, SR), np.int32, fill),
+               k3_term=_filled(B, np.int32, fill))
+    used = np.zeros(2, np.int32)
+    rc = lib().mipx_cut_round_generate_batch(
+        problem._h, B, kc, SR, int(rnd['chunks']), int(rnd['group']), cap, float(rnd['max_term']), int(rnd['max_nonzero_coefs']),
+        float(rnd['min_cut_depth']), float(rnd['cos_parallel']), float(rnd['max_abs_coef']), _ptr(T), _ptr(idx), _ptr(x), _ptr(is_int),
+        _ptr(active), *(_ptr(out[k]) for k, _, _ in shapes), _ptr(out['k2_ncuts']), _ptr(out['k3_nadded']), _ptr(out['k3_added']),
+        _ptr(out['k3_term']), _ptr(used))
+    problem.ctx.check(rc, 'mipx_cut_round_generate_batch')
+    out['chunks'], out['group'] = int(used[0]), int(used[1])
+    return out
 
 
 def solve_multi(ctx, A, b, c, l, u, max_iter=0):

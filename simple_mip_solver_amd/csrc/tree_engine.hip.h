@@ -1620,6 +1620,120 @@ void enqueue_finish(const mipx::FinishArgs &g, const mipx::PcApplyArgs *a, hipSt
     }
 }
 
+// Everything the six kernels of a cut round read and write, as device pointers: the engine fills one from its tree
+// and step buffers (cut_round_data below), mipx_cut_round_*_batch of cutround_api.hip.h from a caller's arrays.
+struct CutRoundData {
+    int n = 0, m0 = 0, mstride = 0, kc = 0, B = 0, slab_rows = 0;
+    // cut_round_begin
+    int round = 0, max_rounds = 0, have_dump = 0;
+    double progress_tol = 0.0, max_dual_bound = 0.0;
+    const int32_t *status = nullptr, *mipf = nullptr;
+    const double *obj = nullptr, *y = nullptr;
+    int8_t *vstat = nullptr;
+    int32_t *ncut = nullptr, *ids = nullptr, *state = nullptr;
+    double *obj_before = nullptr;
+    int32_t *active = nullptr, *resolve = nullptr, *need_tab = nullptr, *counters = nullptr;
+    // K2, pool_append, K3, cut_round_apply
+    const double *A = nullptr, *b = nullptr, *T = nullptr, *x = nullptr;
+    const int32_t *idx = nullptr;
+    const uint8_t *is_int = nullptr;
+    double max_term = 0.0, min_cut_depth = 0.0, cos_parallel = 0.0, max_abs_coef = 0.0;
+    int max_nonzero_coefs = 0, mfma = 0;
+    double *slab_pi = nullptr, *slab_pi0 = nullptr;
+    int32_t *pool_list = nullptr;
+    double *store_pi = nullptr, *store_pi0 = nullptr;
+    int32_t *store_count = nullptr;
+    int store_cap = 0;
+    int32_t *k2_ncuts = nullptr, *k3_nadded = nullptr, *k3_added = nullptr, *k3_term = nullptr;
+};
+
+// The first half of a cut round as launches on st: with `gather` the working copies of the nodes' cut lists first
+// (cut_gather_state, the start of a step), then cut_round_begin.  The one place the two are launched from (the
+// engine's step start and tree_cut_rounds, and mipx_cut_round_begin_batch on caller data).
+int enqueue_cut_begin(mipx_ctx *ctx, const CutRoundData &d, const mipx::CutGatherArgs *gather, bool begin, hipStream_t st) {
+    if (gather != nullptr) {
+        hipLaunchKernelGGL(mipx::cut_gather_state, dim3(d.B), dim3(64), 0, st, *gather);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (!begin) return MIPX_OK;
+    mipx::CutRoundArgs ra;
+    ra.n = d.n; ra.m0 = d.m0; ra.mstride = d.mstride; ra.kc = d.kc; ra.batch = d.B; ra.round = d.round;
+    ra.max_rounds = d.max_rounds;
+    ra.progress_tol = d.progress_tol; ra.max_dual_bound = d.max_dual_bound;
+    ra.status = d.status; ra.obj = d.obj; ra.mipf = d.mipf; ra.y = d.y; ra.vstat = d.vstat;
+    ra.ncut = d.ncut; ra.ids = d.ids; ra.state = d.state; ra.obj_before = d.obj_before;
+    ra.active = d.active; ra.resolve = d.resolve; ra.counters = d.counters;
+    ra.have_dump = d.have_dump; ra.need_tab = d.need_tab;
+    hipLaunchKernelGGL(mipx::cut_round_begin, dim3(d.B), dim3(64), 0, st, ra);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
+// The workgroups per node and the cuts per group K2 runs with: 0 asks for the engine's rule (few nodes: their cuts
+// spread over more workgroups; the largest group whose staging fits the LDS that many workgroups leave each other).
+void cut_launch_shape(const CutRoundData &d, int &chunks, int &group) {
+    if (chunks == 0) chunks = d.B >= 256 ? 1 : (d.B >= 32 ? 4 : 16);
+    if (group == 0) group = mipx::gomory_group(d.n, d.mstride, (long)d.B * chunks);
+}
+
+// The second half as launches on st: K2 into the nodes' slabs, pool_append, K3 over the pool lists, cut_round_apply.
+// The one place the four are launched from in their engine form.  marks (optional): three events, recorded before
+// K2, behind it and behind K3 (the engine's k2_ms / k3_ms).
+int enqueue_cut_generate(mipx_ctx *ctx, const CutRoundData &d, int chunks, int group, hipStream_t st,
+                         const hipEvent_t *marks = nullptr) {
+    const int B = d.B, n = d.n;
+    cut_launch_shape(d, chunks, group);
+    mipx::GomoryArgs ga;
+    ga.m = d.m0; ga.n = n; ga.batch = B;
+    ga.A = d.A; ga.b = d.b;
+    ga.T = d.T; ga.idx = d.idx; ga.x = d.x; ga.is_int = d.is_int;
+    ga.max_term = d.max_term;
+    ga.ncuts = d.k2_ncuts; ga.row_idx = nullptr; ga.pi = nullptr; ga.pi0 = nullptr;
+    ga.safe_pi = nullptr; ga.safe_pi0 = nullptr;
+    ga.chunks = chunks;
+    ga.ncut = d.ncut; ga.cut_ids = d.ids; ga.cut_pi = d.store_pi; ga.cut_pi0 = d.store_pi0;
+    ga.cut_stride = d.kc; ga.mstride = d.mstride; ga.vstat = d.vstat; ga.clip_x = 1;
+    ga.active = d.active;
+    ga.slab_pi = d.slab_pi; ga.slab_pi0 = d.slab_pi0;
+    ga.slab_n = d.state + (size_t)mipx::CF_SLAB_N * B; ga.slab_rows = d.slab_rows;
+    ga.group = group;
+    ga.mfma = d.mfma;
+    const size_t lds2 = mipx::gomory_lds_bytes(n, d.mstride, ga.group);
+    if (marks) HIP_TRY(ctx, hipEventRecord(marks[0], st));
+    if (lds2 > 64 * 1024)
+        HIP_TRY(ctx, hipFuncSetAttribute((const void *)mipx::gomory_cuts<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    hipLaunchKernelGGL((mipx::gomory_cuts<256>), dim3(B * ga.chunks), dim3(256), lds2, st, ga);
+    HIP_TRY(ctx, hipGetLastError());
+    if (marks) HIP_TRY(ctx, hipEventRecord(marks[1], st));
+    mipx::PoolAppendArgs pa;
+    pa.batch = B; pa.slab_rows = d.slab_rows; pa.active = d.active; pa.k2_ncuts = d.k2_ncuts;
+    pa.state = d.state; pa.pool_list = d.pool_list;
+    hipLaunchKernelGGL(mipx::pool_append, dim3((B + 63) / 64), dim3(64), 0, st, pa);
+    HIP_TRY(ctx, hipGetLastError());
+    mipx::SelectArgs sa;
+    sa.n = n; sa.batch = B; sa.kmax = d.slab_rows;
+    sa.npool = d.state + (size_t)mipx::CF_POOL_N * B; sa.pi = d.slab_pi; sa.pi0 = d.slab_pi0; sa.x = d.x;
+    sa.max_nonzero_coefs = d.max_nonzero_coefs; sa.min_cut_depth = d.min_cut_depth;
+    sa.cos_parallel = d.cos_parallel; sa.max_abs_coef = d.max_abs_coef;
+    sa.nadded = d.k3_nadded; sa.added = d.k3_added; sa.terminator = d.k3_term; sa.depth = nullptr;
+    sa.pool_list = d.pool_list; sa.clip_x = 1; sa.active = d.active;
+    const size_t lds3 = (size_t)d.slab_rows * (3 * 8 + 2 * 4) + 16 + 64;
+    hipLaunchKernelGGL(mipx::select_cuts, dim3(B), dim3(256), lds3, st, sa);
+    HIP_TRY(ctx, hipGetLastError());
+    if (marks) HIP_TRY(ctx, hipEventRecord(marks[2], st));
+    mipx::CutApplyArgs aa;
+    aa.n = n; aa.m0 = d.m0; aa.mstride = d.mstride; aa.kc = d.kc; aa.batch = B; aa.slab_rows = d.slab_rows;
+    aa.active = d.active; aa.k3_nadded = d.k3_nadded; aa.k3_added = d.k3_added;
+    aa.slab_pi = d.slab_pi; aa.slab_pi0 = d.slab_pi0; aa.pool_list = d.pool_list;
+    aa.vstat = d.vstat; aa.ncut = d.ncut; aa.ids = d.ids; aa.state = d.state;
+    aa.store_pi = d.store_pi; aa.store_pi0 = d.store_pi0; aa.store_count = d.store_count;
+    aa.store_cap = d.store_cap;
+    aa.resolve = d.resolve; aa.counters = d.counters;
+    hipLaunchKernelGGL(mipx::cut_round_apply, dim3(B), dim3(256), 0, st, aa);
+    HIP_TRY(ctx, hipGetLastError());
+    return MIPX_OK;
+}
+
 // the kernels that finish a step on the device, queued behind its scoring
 int launch_finish(mipx_tree *t, StepBuf &S) {
     mipx_ctx *ctx = t->ctx;
@@ -2030,8 +2144,9 @@ int tree_launch(mipx_tree *t, StepBuf &S, int want) {
         ga.batch = B; ga.kc = t->kc; ga.slot = S.d_slot;
         ga.pool_ncut = t->pool_ncut; ga.pool_ids = t->pool_ids;
         ga.ncut = S.w_ncut; ga.ids = S.w_ids; ga.state = S.cs_state; ga.counters = S.cs_counters;
-        hipLaunchKernelGGL(mipx::cut_gather_state, dim3(B), dim3(64), 0, st, ga);
-        HIP_TRY(ctx, hipGetLastError());
+        CutRoundData cd;
+        cd.B = B;
+        if ((rc = enqueue_cut_begin(ctx, cd, &ga, false, st))) return rc;   // (the gather alone: the node LPs come first)
         int maxc = 0;
         for (int k = 0; k < B; k++) maxc = std::max(maxc, (int)S.recs[(size_t)k].ncut);
         CutLaunch cl;
@@ -2097,26 +2212,33 @@ int tree_cut_rounds(mipx_tree *t, StepBuf &S) {
     // a launch of its own for the tableau only where a round starts by removing rows.  (exact_tableau:
     // the tableau is refactored from the slack basis like the per-node path's, always by its own launch.)
     const bool fused = t->cp.exact_tableau == 0;
+    CutRoundData cd;
+    cd.n = n; cd.m0 = t->m; cd.mstride = t->mrows; cd.kc = t->kc; cd.B = B; cd.slab_rows = t->slab_rows;
+    cd.max_rounds = t->cp.max_cut_generation_iterations; cd.have_dump = fused ? 1 : 0;
+    cd.progress_tol = t->cp.cutting_plane_progress_tolerance; cd.max_dual_bound = t->cp.max_dual_bound;
+    cd.status = S.d.status; cd.obj = S.d.obj; cd.mipf = S.d.mipf; cd.y = S.d_y; cd.vstat = S.d_vout;
+    cd.ncut = S.w_ncut; cd.ids = S.w_ids; cd.state = S.cs_state; cd.obj_before = S.cs_before;
+    cd.active = S.cs_active; cd.resolve = S.cs_resolve; cd.need_tab = S.cs_need_tab; cd.counters = S.cs_counters;
+    cd.A = t->prob->dA; cd.b = t->prob->db; cd.T = S.dump_T; cd.idx = S.dump_idx; cd.x = S.d_x; cd.is_int = t->d_is_int;
+    cd.max_term = t->cp.max_term; cd.max_nonzero_coefs = t->cp.max_nonzero_coefs; cd.min_cut_depth = t->cp.min_cut_depth;
+    cd.cos_parallel = t->cp.cos_parallel; cd.max_abs_coef = t->cp.max_abs_coef;
+    cd.mfma = (std::getenv("MIPX_K2_MFMA") && std::atoi(std::getenv("MIPX_K2_MFMA"))) ? 1 : 0;   // (experiment: cut_kernels.hip.h)
+    cd.slab_pi = S.slab_pi; cd.slab_pi0 = S.slab_pi0; cd.pool_list = S.pool_list;
+    cd.store_pi = t->store_pi; cd.store_pi0 = t->store_pi0; cd.store_count = t->store_count;
+    cd.store_cap = (int)(t->store_cap - t->cm_rows);   // (the migration region is not K3's)
+    cd.k2_ncuts = S.k2_ncuts; cd.k3_nadded = S.k3_nadded; cd.k3_added = S.k3_added; cd.k3_term = S.k3_term;
     for (int round = 0;; round++) {
         HIP_TRY(ctx, hipMemsetAsync(S.cs_counters, 0, 8, st));   // n_active, n_changed (max_ncut stays)
         HIP_TRY(ctx, hipMemsetAsync(S.cs_counters + 3, 0, 4, st));   // n_need_tab
-        mipx::CutRoundArgs ra;
-        ra.n = n; ra.m0 = t->m; ra.mstride = t->mrows; ra.kc = t->kc; ra.batch = B; ra.round = round;
-        ra.max_rounds = t->cp.max_cut_generation_iterations;
-        ra.progress_tol = t->cp.cutting_plane_progress_tolerance; ra.max_dual_bound = t->cp.max_dual_bound;
-        ra.status = S.d.status; ra.obj = S.d.obj; ra.mipf = S.d.mipf; ra.y = S.d_y; ra.vstat = S.d_vout;
-        ra.ncut = S.w_ncut; ra.ids = S.w_ids; ra.state = S.cs_state; ra.obj_before = S.cs_before;
-        ra.active = S.cs_active; ra.resolve = S.cs_resolve; ra.counters = S.cs_counters;
-        ra.have_dump = fused ? 1 : 0; ra.need_tab = S.cs_need_tab;
-        hipLaunchKernelGGL(mipx::cut_round_begin, dim3(B), dim3(64), 0, st, ra);
-        HIP_TRY(ctx, hipGetLastError());
+        cd.round = round;
+        int rc = enqueue_cut_begin(ctx, cd, nullptr, true, st);
+        if (rc) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(S.h_cs, S.cs_counters, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
         if (cnt[CutState::kActive] == 0) break;   // nobody generates any more
         // the tableau of every generating node's basis (refactorisation from the slack basis -- or,
         // without exact_tableau, from the root's anchor where the node has no cut rows -- then zero
         // iterations: the basis is optimal), dumped for K2
-        int rc = MIPX_OK;
         if (cnt[CutState::kNeedTab] > 0) {
             CutLaunch cl;
             cl.ncut = S.w_ncut; cl.ids = S.w_ids; cl.vstat_by_node = 1; cl.active = S.cs_need_tab;
@@ -2126,54 +2248,8 @@ int tree_cut_rounds(mipx_tree *t, StepBuf &S) {
                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &cl);
             if (rc) return rc;
         }
-        mipx::GomoryArgs ga;
-        ga.m = t->m; ga.n = n; ga.batch = B;
-        ga.A = t->prob->dA; ga.b = t->prob->db;
-        ga.T = S.dump_T; ga.idx = S.dump_idx; ga.x = S.d_x; ga.is_int = t->d_is_int;
-        ga.max_term = t->cp.max_term;
-        ga.ncuts = S.k2_ncuts; ga.row_idx = nullptr; ga.pi = nullptr; ga.pi0 = nullptr;
-        ga.safe_pi = nullptr; ga.safe_pi0 = nullptr;
-        ga.chunks = B >= 256 ? 1 : (B >= 32 ? 4 : 16);
-        ga.ncut = S.w_ncut; ga.cut_ids = S.w_ids; ga.cut_pi = t->store_pi; ga.cut_pi0 = t->store_pi0;
-        ga.cut_stride = t->kc; ga.mstride = t->mrows; ga.vstat = S.d_vout; ga.clip_x = 1;
-        ga.active = S.cs_active;
-        ga.slab_pi = S.slab_pi; ga.slab_pi0 = S.slab_pi0;
-        ga.slab_n = S.cs_state + (size_t)mipx::CF_SLAB_N * B; ga.slab_rows = t->slab_rows;
-        ga.group = mipx::gomory_group(n, t->mrows, (long)B * ga.chunks);
-        ga.mfma = (std::getenv("MIPX_K2_MFMA") && std::atoi(std::getenv("MIPX_K2_MFMA"))) ? 1 : 0;   // (experiment: cut_kernels.hip.h)
-        const size_t lds2 = mipx::gomory_lds_bytes(n, t->mrows, ga.group);
-        HIP_TRY(ctx, hipEventRecord(S.k2a, st));
-        if (lds2 > 64 * 1024)
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)mipx::gomory_cuts<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        hipLaunchKernelGGL((mipx::gomory_cuts<256>), dim3(B * ga.chunks), dim3(256), lds2, st, ga);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipEventRecord(S.k2b, st));
-        mipx::PoolAppendArgs pa;
-        pa.batch = B; pa.slab_rows = t->slab_rows; pa.active = S.cs_active; pa.k2_ncuts = S.k2_ncuts;
-        pa.state = S.cs_state; pa.pool_list = S.pool_list;
-        hipLaunchKernelGGL(mipx::pool_append, dim3((B + 63) / 64), dim3(64), 0, st, pa);
-        HIP_TRY(ctx, hipGetLastError());
-        mipx::SelectArgs sa;
-        sa.n = n; sa.batch = B; sa.kmax = t->slab_rows;
-        sa.npool = S.cs_state + (size_t)mipx::CF_POOL_N * B; sa.pi = S.slab_pi; sa.pi0 = S.slab_pi0; sa.x = S.d_x;
-        sa.max_nonzero_coefs = t->cp.max_nonzero_coefs; sa.min_cut_depth = t->cp.min_cut_depth;
-        sa.cos_parallel = t->cp.cos_parallel; sa.max_abs_coef = t->cp.max_abs_coef;
-        sa.nadded = S.k3_nadded; sa.added = S.k3_added; sa.terminator = S.k3_term; sa.depth = nullptr;
-        sa.pool_list = S.pool_list; sa.clip_x = 1; sa.active = S.cs_active;
-        const size_t lds3 = (size_t)t->slab_rows * (3 * 8 + 2 * 4) + 16 + 64;
-        hipLaunchKernelGGL(mipx::select_cuts, dim3(B), dim3(256), lds3, st, sa);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipEventRecord(S.k3b, st));
-        mipx::CutApplyArgs aa;
-        aa.n = n; aa.m0 = t->m; aa.mstride = t->mrows; aa.kc = t->kc; aa.batch = B; aa.slab_rows = t->slab_rows;
-        aa.active = S.cs_active; aa.k3_nadded = S.k3_nadded; aa.k3_added = S.k3_added;
-        aa.slab_pi = S.slab_pi; aa.slab_pi0 = S.slab_pi0; aa.pool_list = S.pool_list;
-        aa.vstat = S.d_vout; aa.ncut = S.w_ncut; aa.ids = S.w_ids; aa.state = S.cs_state;
-        aa.store_pi = t->store_pi; aa.store_pi0 = t->store_pi0; aa.store_count = t->store_count;
-        aa.store_cap = (int)(t->store_cap - t->cm_rows);   // (the migration region is not K3's)
-        aa.resolve = S.cs_resolve; aa.counters = S.cs_counters;
-        hipLaunchKernelGGL(mipx::cut_round_apply, dim3(B), dim3(256), 0, st, aa);
-        HIP_TRY(ctx, hipGetLastError());
+        const hipEvent_t marks[3] = {S.k2a, S.k2b, S.k3b};
+        if ((rc = enqueue_cut_generate(ctx, cd, 0, 0, st, marks))) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(S.h_cs, S.cs_counters, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
         {   // (the stream is idle: the round's kernel times for the roofline entries of the cut configs)
@@ -4623,3 +4699,4 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "lpdive_api.hip.h"
 #include "objstep_api.hip.h"
 #include "finish_api.hip.h"
+#include "cutround_api.hip.h"

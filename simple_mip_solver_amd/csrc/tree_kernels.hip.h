@@ -227,7 +227,8 @@ struct CutGatherArgs {
     const int32_t *pool_ncut, *pool_ids;     // node pool
     int32_t *ncut, *ids;                     // working lists (dense)
     int32_t *state;                          // CF_FIELDS x batch, zeroed here
-    int32_t *counters;                       // [n_active, n_changed, max_ncut, -]: max_ncut initialised here
+    int32_t *counters;                       // [n_active, n_changed, max_ncut, -]: max_ncut raised here (atomicMax; the
+                                             //   engine's memset at the start of a step clears it, not this kernel)
 };
 __global__ __launch_bounds__(64) void cut_gather_state(CutGatherArgs g) {
     const int k = blockIdx.x, lane = threadIdx.x;
