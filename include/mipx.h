@@ -550,5 +550,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_lpdive.h" /* LP diving: fix a column, re-solve the batch of LPs, repeat */
 #include "mipx_finish.h" /* test scaffolding: the device finish of a frontier step on a caller's data */
 #include "mipx_cutround.h" /* test scaffolding: the kernels of a cut round on a caller's data */
+#include "mipx_cglp_screen.h" /* support sessions that keep their duals: dual screen of the leaves, cold retry */
 
 #endif /* MIPX_H */

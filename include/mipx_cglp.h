@@ -26,6 +26,11 @@
  *   [7] leaves of the session after this evaluation
  * then P rows of n + 2: node id, h_t(pi), x_t (a minimiser, n doubles) -- the P leaves of smallest margin in
  * ascending order of (margin, node id), so the rows do not depend on how the launch was scheduled.
+ *
+ * A session may also keep the row duals of its leaves and screen with them: a leaf whose stored duals y+ >= 0 prove
+ * L_t(pi; y+) = y+.b + sum_j min(r_j l_j, r_j u_j) >= pi0 - screen_tol (r = pi - A'y+; L_t <= h_t by weak duality)
+ * gets no LP in that evaluation.  mipx_cglp_screen.h states the bound, its arithmetic and the entries
+ * (mipx_tree_support_open_ex, mipx_tree_support_eval_ex); the two entries below are those with the options off.
  */
 #ifndef MIPX_CGLP_H
 #define MIPX_CGLP_H

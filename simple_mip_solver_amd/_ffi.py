@@ -425,6 +425,17 @@ _CUTROUND_SIGNATURES = {
     'mipx_cut_round_generate_batch': (_i, [_vp] + [_i] * 6 + [_d, _i] + [_d] * 3 + [_vp] * 22),
 }
 CUTROUND_SYMBOLS = list(_CUTROUND_SIGNATURES)
+# ... and those of include/mipx_cglp_screen.h (support sessions that keep their duals: the dual screen of the leaves and
+# the cold retry; mipx_support_screen_batch is test scaffolding), which mipx.h includes
+# (tests/test_cglp_screen_abi.py checks them against that header)
+_CGLP_SCREEN_SIGNATURES = {
+    'mipx_tree_support_open_ex': (_i, [_vp, _vp, _i64, _i, _vp]),
+    'mipx_tree_support_eval_ex': (_i, [_vp, _vp, _d, _d, _d, _i, _i, _vp, _vp, _vp]),
+    'mipx_support_screen_batch': (_i, [_vp, _i64, _vp, _d, _d] + [_vp] * 8),
+}
+CGLP_SCREEN_SYMBOLS = list(_CGLP_SCREEN_SIGNATURES)
+SUPPORT_KEEP_DUALS = 1   # MIPX_SUPPORT_KEEP_DUALS
+CGLP_EXTRA_KEYS = ('screened', 'lp_solved', 'min_screened_margin', 'retried', 'retried_optimal', 'screen_us')
 CUT_FIELDS = ('rounds', 'it_created', 'n_created', 'it_added', 'n_added', 'it_removed', 'n_removed', 'ncut_out', 'stalled',
               'pool_n', 'slab_n', 'dropped')   # CutField of csrc/tree_kernels.hip.h: the rows of a round's state array
 
@@ -449,7 +460,7 @@ def lib():
                                       list(_FIXPROP_SIGNATURES.items()) + list(_WREPAIR_SIGNATURES.items()) +
                                       list(_CUBE_SIGNATURES.items()) + list(_COMPLETE_SIGNATURES.items()) +
                                       list(_LPDIVE_SIGNATURES.items()) + list(_FINISH_SIGNATURES.items()) +
-                                      list(_CUTROUND_SIGNATURES.items())):
+                                      list(_CUTROUND_SIGNATURES.items()) + list(_CGLP_SCREEN_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -1095,6 +1106,24 @@ class Problem:
         self.ctx.check(rc, 'mipx_weighted_repair_batch')
         return dict(x=xo, obj=obj, status=status, counts=counts)
 
+    def support_screen_batch(self, pi, pi0, screen_tol, l, u, y, has_y):
+        """The dual screen and the pack of a support evaluation on host buffers (mipx_support_screen_batch,
+        include/mipx_cglp_screen.h; test scaffolding): pi (n), l, u (T, n) the leaves' boxes, y (T, m) their duals,
+        has_y (T,) which of them count.  Returns dict of bound (T,), screened (T,), packed (T,: positions of the
+        unscreened leaves in ascending order, then -1) and count."""
+        n, m = self.n, self.m
+        pi = np.ascontiguousarray(pi, np.float64).reshape(n)
+        l = np.ascontiguousarray(l, np.float64).reshape(-1, n)
+        T = l.shape[0]
+        u = np.ascontiguousarray(u, np.float64).reshape(T, n)
+        y = np.ascontiguousarray(y, np.float64).reshape(T, m)
+        has_y = np.ascontiguousarray(np.asarray(has_y) != 0, dtype=np.uint8).reshape(T)
+        bound = np.zeros(T); screened = np.zeros(T, np.uint8); packed = np.zeros(T, np.int32); count = np.zeros(1, np.int32)
+        rc = lib().mipx_support_screen_batch(self._h, T, _ptr(pi), float(pi0), float(screen_tol), _ptr(l), _ptr(u), _ptr(y),
+                                             _ptr(has_y), _ptr(bound), _ptr(screened), _ptr(packed), _ptr(count))
+        self.ctx.check(rc, 'mipx_support_screen_batch')
+        return dict(bound=bound, screened=screened, packed=packed, count=int(count[0]))
+
     def cube_search_batch(self, x, l, u, integer_indices, cutoff=np.inf, tol=1e-9, ftol=1e-4,
                           max_columns=DEFAULT_CUBE_SEARCH_COLUMNS, skip=None):
         """The cube search on host buffers (mipx_cube_search_batch, include/mipx_cube.h): x (batch, n) points, l, u the
@@ -1527,10 +1556,12 @@ class Tree:
         d['query_ms'] /= 1000.0
         return d
 
-    def support_open(self, ids):
+    def support_open(self, ids, duals=False):
         """A Support session on the recorded nodes `ids`, the terms of a disjunction (mipx_tree_support_open,
-        include/mipx_cglp.h).  It is closed with the tree at the latest."""
-        s = Support(self, ids)
+        include/mipx_cglp.h).  It is closed with the tree at the latest.  duals=True keeps the leaves' row duals and
+        the buffers of a packed launch, which eval(screen_tol=..., retry_cold=...) needs (MIPX_SUPPORT_KEEP_DUALS of
+        mipx_tree_support_open_ex, include/mipx_cglp_screen.h)."""
+        s = Support(self, ids, duals=duals)
         self._sessions = [r for r in getattr(self, '_sessions', []) if r() is not None] + [weakref.ref(s)]
         return s
 
@@ -1766,25 +1797,43 @@ class Support:
     """The leaves of a disjunction resident on the device, and their support values for a cut direction
     (mipx_support, include/mipx_cglp.h)."""
 
-    def __init__(self, tree, ids):
+    def __init__(self, tree, ids, duals=False):
         self.tree = tree
+        self.duals = bool(duals)
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         h = _vp()
-        tree.problem.ctx.check(lib().mipx_tree_support_open(tree._h, _ptr(ids), len(ids), C.byref(h)),
-                               'mipx_tree_support_open')
+        if self.duals:
+            rc = lib().mipx_tree_support_open_ex(tree._h, _ptr(ids), len(ids), SUPPORT_KEEP_DUALS, C.byref(h))
+        else:
+            rc = lib().mipx_tree_support_open(tree._h, _ptr(ids), len(ids), C.byref(h))
+        tree.problem.ctx.check(rc, 'mipx_tree_support_open')
         self._h = h
 
-    def eval(self, pi, pi0, tol=0.0, max_points=1, want_margins=False):
+    def eval(self, pi, pi0, tol=0.0, max_points=1, want_margins=False, screen_tol=None, retry_cold=False):
         """dict(min_margin, min_id, below, not_optimal, iterations, pivots, leaves, ids, h, x[, margins]): h_t(pi) of
         every leaf against pi0 and the (at most max_points) leaves of smallest margin h_t - pi0, in ascending
-        order of (margin, node id), with a minimiser x of each (mipx_tree_support_eval)."""
+        order of (margin, node id), with a minimiser x of each (mipx_tree_support_eval).
+
+        screen_tol (a number >= 0) screens the leaves by their stored duals first, retry_cold solves the leaves whose
+        LP did not end optimal once more without a basis (mipx_tree_support_eval_ex, include/mipx_cglp_screen.h; both
+        need a session opened with duals=True).  With either, the result also has screened, lp_solved,
+        min_screened_margin, retried, retried_optimal and screen_us; a screened leaf among the rows carries its bound
+        as h and a stale x."""
         n = self.tree.problem.n
         pi = np.ascontiguousarray(pi, np.float64).reshape(n)
         P = int(max_points)
         block = np.zeros(CGLP_HEAD + P * (n + 2))
         margins = np.zeros(self.leaves_count()) if want_margins else None
-        self.tree.problem.ctx.check(lib().mipx_tree_support_eval(self._h, _ptr(pi), float(pi0), float(tol), P, _ptr(block),
-                                                                 _ptr(margins)), 'mipx_tree_support_eval')
+        extended = screen_tol is not None or retry_cold
+        if extended:
+            extra = np.zeros(len(CGLP_EXTRA_KEYS))
+            rc = lib().mipx_tree_support_eval_ex(self._h, _ptr(pi), float(pi0), float(tol),
+                                                 -1.0 if screen_tol is None else float(screen_tol), int(bool(retry_cold)), P,
+                                                 _ptr(block), _ptr(margins), _ptr(extra))
+            self.tree.problem.ctx.check(rc, 'mipx_tree_support_eval_ex')
+        else:
+            self.tree.problem.ctx.check(lib().mipx_tree_support_eval(self._h, _ptr(pi), float(pi0), float(tol), P, _ptr(block),
+                                                                     _ptr(margins)), 'mipx_tree_support_eval')
         k = int(block[3])
         rows = block[CGLP_HEAD:CGLP_HEAD + k * (n + 2)].reshape(k, n + 2)
         out = dict(min_margin=float(block[0]), min_id=int(block[1]), below=int(block[2]), not_optimal=int(block[4]),
@@ -1792,6 +1841,9 @@ class Support:
                    ids=rows[:, 0].astype(np.int64), h=rows[:, 1].copy(), x=rows[:, 2:].copy())
         if want_margins:
             out['margins'] = margins[:out['leaves']]
+        if extended:
+            out.update((key, float(v) if key in ('min_screened_margin', 'screen_us') else int(v))
+                       for key, v in zip(CGLP_EXTRA_KEYS, extra))
         return out
 
     def leaves_count(self):

@@ -33,6 +33,7 @@
 #include "prop_kernels.hip.h"
 #include "rcfix_kernels.hip.h"
 #include "cglp_kernels.hip.h"
+#include "cglp_screen_kernels.hip.h"
 #include "step_layout.h"
 
 struct NodeRec {

@@ -22,6 +22,20 @@ within the tolerance (`stats['converged']`), at `max_rounds`, when every violate
 or when the engine stops a master or a leaf LP at its iteration limit (`stats['master_failed']`,
 `stats['leaf_lps_not_optimal']`: a direction with such a leaf has no certified pi0 and is not used).
 
+Options, all off by default (include/mipx_cglp_screen.h; DESIGN.md 4g.1 has what they measure to):
+
+  screen         the session keeps each leaf's row duals; a round first computes the weak-duality bound
+                 y.b + sum_j min(r_j l_j, r_j u_j), r = pi - A'y, of every leaf, and a leaf whose bound proves its
+                 margin to within half the tolerance gets no LP.  Its margin is the bound's, a lower bound on its own,
+                 so (pi, pi0 + min margin) stays valid; it is never among the rows used (they lie below -tol).
+  stabilisation  lambda, 0 < lambda <= 1 (in-out).  The in-point is a certified cut (pi, pi0 + min margin): the one of
+                 largest violation met, or the last separation point that held on every leaf within tol.  A round
+                 separates at lambda master + (1 - lambda) in (at the master's point before there is an in-point).  A
+                 violated round adds rows and re-solves the master.  A round that holds makes its point the in-point:
+                 converged if v_in - v_master <= tol max(1, |v_master|); else it separates again without solving the
+                 master, and after three such steps in a row at the master's point itself.
+  retry_cold     a leaf LP that did not end optimal is solved once more without a basis before the round counts it.
+
 The two classes normalise differently -- CutGeneratingLP sums the multipliers to one, as the reference does,
 this class boxes pi -- so they return different cuts from the same disjunction; both are valid for it.
 
@@ -42,11 +56,14 @@ FINITE = 1e300   # COIN_INFINITY is 1.8e308: anything at or above this is an inf
 
 class DisjunctiveSeparator:
 
-    def __init__(self, bb, root_id, depth=None, tol=1e-7, max_rounds=500, points_per_round=32, max_master_rows=768):
+    def __init__(self, bb, root_id, depth=None, tol=1e-7, max_rounds=500, points_per_round=32, max_master_rows=768,
+                 screen=False, stabilisation=None, retry_cold=False):
         """bb: a BranchAndBound solved with frontier_batch and tree_record=True; root_id: the node whose subtree
         gives the disjunction; depth: cut the subtree below this many levels; tol: stop when every term holds
         within tol max(1, |pi0|, |pi|_1); max_rounds: separations at most; points_per_round: rows a separation
-        adds to the master at most; max_master_rows: slack rows leave the master above this many."""
+        adds to the master at most; max_master_rows: slack rows leave the master above this many; screen: leaves
+        whose stored duals prove their margin get no LP; stabilisation: the in-out weight of the master's point,
+        0 < lambda <= 1; retry_cold: a leaf LP that did not end optimal is solved once more without a basis."""
         from simple_mip_solver_amd import _ffi
         from simple_mip_solver_amd.algorithms.branch_and_bound import BranchAndBound
         assert isinstance(bb, BranchAndBound), 'bb must be a BranchAndBound instance'
@@ -64,6 +81,7 @@ class DisjunctiveSeparator:
             f'points_per_round is an integer from 1 to {_ffi.CGLP_MAX_POINTS}'
         self.bb, self.root_id, self.depth = bb, int(root_id), depth
         self.tol, self.max_rounds, self.points_per_round = float(tol), max_rounds, points_per_round
+        self._set_options(screen, stabilisation, retry_cold)
         if self.root_id == 0:
             lo, up = (np.asarray(a, np.float64) for a in (bb.root_node.lp.variablesLower, bb.root_node.lp.variablesUpper))
         else:
@@ -76,17 +94,25 @@ class DisjunctiveSeparator:
         self.max_master_rows = int(max_master_rows)
         self.R = float(np.maximum(np.abs(lo), np.abs(up)).sum())   # |h_t(pi)| <= R for every pi of the box
         self.leaf_ids = self._terms()
-        self._session = bb._native.support_open(self.leaf_ids) if len(self.leaf_ids) else None
+        if not len(self.leaf_ids):
+            self._session = None
+        elif self.screen or self.retry_cold:   # (the duals and the buffers of a packed launch stay on the device)
+            self._session = bb._native.support_open(self.leaf_ids, duals=True)
+        else:
+            self._session = bb._native.support_open(self.leaf_ids)
         self.dropped_ids = np.zeros(0, np.int64)   # the terms the session found empty (LP infeasible)
         self.best_cut = None   # (pi, pi0) of the last solve(): the valid cut of largest violation met, violated or not
         self.stats = None
         self.timing = None     # wall seconds of the last solve(): dict(separation, master)
 
     @classmethod
-    def on_session(cls, session, lo, up, tol=1e-7, max_rounds=500, points_per_round=32, max_master_rows=768):
+    def on_session(cls, session, lo, up, tol=1e-7, max_rounds=500, points_per_round=32, max_master_rows=768,
+                   screen=False, stabilisation=None, retry_cold=False):
         """A separator on an open _ffi.Support session whose leaves all lie in the box lo <= x <= up (no
-        BranchAndBound: solve() then needs its x_star)."""
+        BranchAndBound: solve() then needs its x_star).  screen and retry_cold need a session opened with
+        duals=True."""
         self = object.__new__(cls)
+        self._set_options(screen, stabilisation, retry_cold)
         self.bb, self.root_id, self.depth = None, None, None
         self.tol, self.max_rounds, self.points_per_round = float(tol), int(max_rounds), int(points_per_round)
         self.max_master_rows = int(max_master_rows)
@@ -95,6 +121,14 @@ class DisjunctiveSeparator:
         self._session, self.leaf_ids = session, session.leaves()
         self.dropped_ids, self.best_cut, self.stats, self.timing = np.zeros(0, np.int64), None, None, None
         return self
+
+    def _set_options(self, screen, stabilisation, retry_cold):
+        assert isinstance(screen, bool) and isinstance(retry_cold, bool), 'screen and retry_cold are bool'
+        if stabilisation is not None:
+            assert isinstance(stabilisation, (int, float)) and 0 < stabilisation <= 1, \
+                'stabilisation is None or the weight of the master\'s point, 0 < lambda <= 1'
+        self.screen, self.retry_cold = screen, retry_cold
+        self.stabilisation = None if stabilisation is None else float(stabilisation)
 
     def _terms(self):
         tree = self.bb.tree
@@ -152,6 +186,10 @@ class DisjunctiveSeparator:
         stats = dict(rounds=0, leaf_lps=0, pivots=0, points=0, master_rows_dropped=0, master_rows=0,
                      final_min_margin=None, violation=None, leaves=len(self.leaf_ids), dropped=0, converged=False,
                      master_failed=False, leaf_lps_not_optimal=0)
+        lam = self.stabilisation
+        extended = self.screen or self.retry_cold or lam is not None
+        if extended:
+            stats.update(screened=0, in_moves=0, retried=0, retried_optimal=0)
         self.stats = stats
         self.timing = timing = dict(separation=0.0, master=0.0)
         if self._session is None:
@@ -159,16 +197,32 @@ class DisjunctiveSeparator:
         ses = self._session
         before = ses.stats()
         # without a row the master says pi = -sign(x*), pi0 = R: the first separation starts from there
-        pi, pi0 = np.where(x_star > 0, -1.0, 1.0), self.R
+        pi_m, pi0_m = np.where(x_star > 0, -1.0, 1.0), self.R
         X = np.zeros((0, n))
         seen = set()
         basis, best = None, None
+        # in-out (stabilisation = lambda): the in-point is a certified cut, a round separates between it and the master's
+        inp, inp_violation, in_steps, at_master = None, None, 0, False
         for _ in range(self.max_rounds):
+            at_master = at_master or lam is None or inp is None
+            if at_master:
+                pi, pi0 = pi_m, pi0_m
+            else:
+                pi, pi0 = lam * pi_m + (1.0 - lam) * inp[0], lam * pi0_m + (1.0 - lam) * inp[1]
             scale = max(1.0, abs(pi0), float(np.abs(pi).sum()))
+            options = {}
+            if self.screen:   # (half the tolerance: a screened leaf is never among the violated rows)
+                options['screen_tol'] = self.tol * scale / 2
+            if self.retry_cold:
+                options['retry_cold'] = True
             t0 = time.perf_counter()
-            res = ses.eval(pi, pi0, tol=self.tol * scale, max_points=self.points_per_round)
+            res = ses.eval(pi, pi0, tol=self.tol * scale, max_points=self.points_per_round, **options)
             timing['separation'] += time.perf_counter() - t0
             stats['rounds'] += 1
+            if extended:
+                stats['screened'] += res.get('screened', 0)
+                stats['retried'] += res.get('retried', 0)
+                stats['retried_optimal'] += res.get('retried_optimal', 0)
             if res['leaves'] == 0:
                 break
             if res['not_optimal']:   # a leaf LP hit its iteration limit: this pi has no certified pi0; the best cut so far stands
@@ -179,10 +233,25 @@ class DisjunctiveSeparator:
             violation = h_min - float(x_star @ pi)
             if best is None or violation > best[0]:
                 best = (violation, pi.copy(), h_min)
+            if lam is not None and (inp is None or violation > inp_violation):
+                inp, inp_violation = (pi.copy(), h_min), violation
+                stats['in_moves'] += 1
             stats['final_min_margin'] = res['min_margin']
             if res['min_margin'] >= -self.tol * scale:
-                stats['converged'] = True
-                break
+                if at_master:
+                    stats['converged'] = True
+                    break
+                # the separation point holds on every leaf: it is the in-point now, with its certified pi0
+                if inp_violation != violation:
+                    inp, inp_violation = (pi.copy(), h_min), violation
+                    stats['in_moves'] += 1
+                v_master = float(x_star @ pi_m - pi0_m)
+                if -violation - v_master <= self.tol * max(1.0, abs(v_master)):
+                    stats['converged'] = True
+                    break
+                in_steps += 1
+                at_master = in_steps >= 3   # (closer by 1 - lambda a step: then at the master's point itself)
+                continue
             new = []
             for k in range(len(res['ids'])):
                 if res['h'][k] - pi0 >= -self.tol * scale:
@@ -192,7 +261,10 @@ class DisjunctiveSeparator:
                     seen.add(key)
                     new.append(res['x'][k])
             if not new:
-                break   # (every violated point is a row already: the master cannot move; the best cut stands)
+                if at_master:
+                    break   # (every violated point is a row already: the master cannot move; the best cut stands)
+                at_master = True   # (... of this separation point: the master's own may still give new ones)
+                continue
             if len(X) + len(new) > self.max_master_rows and basis is not None:
                 slack = basis[1] == 1
                 stats['master_rows_dropped'] += int(slack.sum())
@@ -209,7 +281,8 @@ class DisjunctiveSeparator:
             if master is None:   # the engine gave the master up: the best valid cut met so far stands
                 stats['master_failed'] = True
                 break
-            pi, pi0, _, _, basis = master
+            pi_m, pi0_m, _, _, basis = master
+            in_steps, at_master = 0, False
         after = ses.stats()
         self.dropped_ids = ses.leaves(dropped=True)
         stats.update(leaf_lps=after['leaf_lps'] - before['leaf_lps'], pivots=after['pivots'] - before['pivots'],
