@@ -434,6 +434,19 @@ _CGLP_SCREEN_SIGNATURES = {
     'mipx_support_screen_batch': (_i, [_vp, _i64, _vp, _d, _d] + [_vp] * 8),
 }
 CGLP_SCREEN_SYMBOLS = list(_CGLP_SCREEN_SIGNATURES)
+# ... and that of include/mipx_mir.h (MIR cuts: batched separation of base rows), which mipx.h includes
+# (tests/test_mir_abi.py checks it against that header)
+_MIR_SIGNATURES = {
+    'mipx_mir_separate_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _vp, _i, _vp, _i, _d, _d, _d] + [_vp] * 6),
+}
+MIR_SYMBOLS = list(_MIR_SIGNATURES)
+MIR_STATUS = {0: 'cut', 1: 'no_trial', 2: 'shallow', 3: 'dynamism', 4: 'skipped'}   # MIPX_MIR_* of the header
+# the defaults of the separation: divisor candidates per row (at most MIR_MAX_DIVISORS), the window of f0, the largest
+# ratio of a cut's coefficients
+MIR_MAX_DIVISORS = 64
+DEFAULT_MIR_DIVISORS = 16
+DEFAULT_MIR_F0_MIN = 0.05
+DEFAULT_MIR_DYNAMISM = 1e6
 SUPPORT_KEEP_DUALS = 1   # MIPX_SUPPORT_KEEP_DUALS
 CGLP_EXTRA_KEYS = ('screened', 'lp_solved', 'min_screened_margin', 'retried', 'retried_optimal', 'screen_us')
 CUT_FIELDS = ('rounds', 'it_created', 'n_created', 'it_added', 'n_added', 'it_removed', 'n_removed', 'ncut_out', 'stalled',
@@ -460,7 +473,8 @@ def lib():
                                       list(_FIXPROP_SIGNATURES.items()) + list(_WREPAIR_SIGNATURES.items()) +
                                       list(_CUBE_SIGNATURES.items()) + list(_COMPLETE_SIGNATURES.items()) +
                                       list(_LPDIVE_SIGNATURES.items()) + list(_FINISH_SIGNATURES.items()) +
-                                      list(_CUTROUND_SIGNATURES.items()) + list(_CGLP_SCREEN_SIGNATURES.items())):
+                                      list(_CUTROUND_SIGNATURES.items()) + list(_CGLP_SCREEN_SIGNATURES.items()) +
+                                      list(_MIR_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -1199,6 +1213,34 @@ class Problem:
                                         _ptr(lo), _ptr(uo), _ptr(status), _ptr(changed), _ptr(rounds))
         self.ctx.check(rc, 'mipx_propagate_batch')
         return dict(l=lo, u=uo, status=status, changed=changed, rounds=rounds)
+
+    def mir_separate_batch(self, x, l, u, integer_indices, row_integral=None, multipliers=None,
+                           max_divisors=DEFAULT_MIR_DIVISORS, f0_min=DEFAULT_MIR_F0_MIN, min_efficacy=1e-8,
+                           max_dynamism=DEFAULT_MIR_DYNAMISM):
+        """MIR separation on host buffers (mipx_mir_separate_batch, include/mipx_mir.h): x, l, u (batch, n) points and
+        boxes, row_integral m flags or None, multipliers None (the m unit rows) or an (R, m) matrix shared by the
+        points.  Returns dict of pi (batch, R, n), pi0, efficacy, delta, sign, status (MIR_STATUS codes; batch, R each)
+        and kernel_us, the device time of the kernel."""
+        n, m = self.n, self.m
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n)
+        B = x.shape[0]
+        l = np.ascontiguousarray(l, dtype=np.float64).reshape(-1, n)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, n)
+        assert l.shape[0] == B and u.shape[0] == B, 'x, l and u hold the same number of rows'
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        ri = _arr(row_integral, np.uint8, m)
+        mult = _arr(multipliers, np.float64, (-1, m))
+        R = m if mult is None else mult.shape[0]
+        pi = np.zeros((B, R, n)); pi0 = np.zeros((B, R)); eff = np.zeros((B, R)); delta = np.zeros((B, R))
+        sign = np.zeros((B, R), np.int32); status = np.zeros((B, R), np.int32)
+        rc = lib().mipx_mir_separate_batch(self._h, B, _ptr(x), _ptr(l), _ptr(u), _ptr(ii), len(ii), _ptr(ri),
+                                           0 if mult is None else R, _ptr(mult), int(max_divisors), float(f0_min),
+                                           float(min_efficacy), float(max_dynamism), _ptr(pi), _ptr(pi0), _ptr(eff),
+                                           _ptr(delta), _ptr(sign), _ptr(status))
+        self.ctx.check(rc, 'mipx_mir_separate_batch')
+        ms = self.ctx.last_kernel_ms() if B else 0.0
+        return dict(pi=pi, pi0=pi0, efficacy=eff, delta=delta, sign=sign, status=status,
+                    kernel_us=max(ms, 0.0) * 1e3)
 
     def reduced_cost_tighten_batch(self, l, u, y, integer_indices, cutoff, tol=RCFIX_TOL, dtol=RCFIX_DTOL, in_place=False):
         """Reduced-cost bound tightening on host buffers (mipx_reduced_cost_tighten_batch, include/mipx_rcfix.h):

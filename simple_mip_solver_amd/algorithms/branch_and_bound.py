@@ -127,7 +127,7 @@ class BranchAndBound(BaseAlgorithm):
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
                  propagate=None, reduced_cost=None, objective_step=None, local_search=None, fix_propagate=None,
                  weighted_repair=None, cube_search=None, complete_continuous=None, lp_dive=None, lp_dive_every=None,
-                 **kwargs):
+                 root_cuts=None, root_cut_rows=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -263,7 +263,16 @@ class BranchAndBound(BaseAlgorithm):
         is then completed and checked as complete_continuous does.  It runs in the steps in which the search holds no
         incumbent, and with lp_dive_every=k (a positive integer; default None) in every k-th step as well.  A feasible
         point competes for the step's incumbent behind the other families.  Inherited by restart() with
-        primal_heuristic.  Counters: `lp_dive_stats`."""
+        primal_heuristic.  Counters: `lp_dive_stats`.
+        root_cuts (extension; needs frontier_batch and gomory_cuts=False, not with comm, dual_function or tree_record,
+        so not with restart; default None = off): True (10 rounds) or a positive number of rounds.  Before the search
+        starts, rounds of mixed-integer rounding cuts are separated at the root on the GPU (include/mipx_mir.h,
+        utils/mir_cuts.root_cut_loop): the model's rows and the tableau rows of the fractional basic integer columns
+        are the base rows, one workgroup each; the cuts kept, at most root_cut_rows (default 64) of them, are
+        appended to the rows the engine searches on, so every other option sees an ordinary model with m + k rows.
+        The cuts are valid by construction: the optimum is the same, the root bound is at least as good, the nodes
+        evaluated differ.  `model`, `solution` and every other attribute are those of the model as given.
+        `root_cuts` is then the list of (pi, pi0) kept (pi . x >= pi0); counters: `root_cut_stats`."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -418,6 +427,25 @@ class BranchAndBound(BaseAlgorithm):
         self._lp_dive = lp_dive
         self._lp_dive_every = lp_dive_every
         self.lp_dive_stats = None
+        assert root_cuts is None or root_cuts is True or (
+            isinstance(root_cuts, int) and not isinstance(root_cuts, bool) and root_cuts > 0), \
+            'root_cuts is None, True or a positive number of rounds'
+        assert root_cut_rows is None or (isinstance(root_cut_rows, int) and not isinstance(root_cut_rows, bool) and
+                                         root_cut_rows > 0), 'root_cut_rows is None or a positive number of rows'
+        assert root_cut_rows is None or root_cuts is not None, 'root_cut_rows needs root_cuts'
+        assert root_cuts is None or frontier_batch is not None, \
+            'root_cuts needs frontier_batch (the cut rows are appended to the rows of the native engine)'
+        assert root_cuts is None or comm is None, 'root_cuts cannot be combined with comm'
+        assert root_cuts is None or kwargs.get('gomory_cuts', True) is False, \
+            'root_cuts needs gomory_cuts=False: the cut rounds of a node keep their own rows'
+        assert root_cuts is None or not dual_function, \
+            'root_cuts cannot be combined with dual_function: a cut depends on the right-hand side'
+        assert root_cuts is None or not tree_record, \
+            'root_cuts cannot be combined with tree_record (and so with restart): a cut depends on the right-hand side'
+        self._root_cuts = 10 if root_cuts is True else root_cuts
+        self._root_cut_rows = 64 if root_cut_rows is None else root_cut_rows
+        self.root_cuts = None
+        self.root_cut_stats = None
         if host_spill is True:
             host_spill = os.sysconf('SC_PAGE_SIZE') * os.sysconf('SC_PHYS_PAGES') // 2
         self._host_spill = host_spill
@@ -540,8 +568,19 @@ class BranchAndBound(BaseAlgorithm):
             assert isinstance(backend, HipBackend), 'frontier_batch needs the HIP backend'
             lp = self.root_node.lp
             rs = lp._engine_form()
-            problem = backend._problem(rs.A, rs.b, rs.c, rs.key)
             l, u = lp._bounds()
+            if self._root_cuts:
+                # the rows the engine searches on: the model's and the cuts the root loop keeps; everything behind
+                # this point sees an ordinary model (the key names the cut rows, so another row set is another problem)
+                from simple_mip_solver_amd.utils.mir_cuts import root_cut_loop
+                loop = root_cut_loop(rs.A, rs.b, rs.c, l, u, self.model.integerIndices, rounds=self._root_cuts,
+                                     max_rows=self._root_cut_rows)
+                self.root_cuts = loop['cuts']
+                self.root_cut_stats = loop['stats']
+                problem = backend._problem(loop['A'], loop['b'], rs.c, ('root_cuts', rs.key, loop['A'][rs.A.shape[0]:].tobytes(),
+                                                                      loop['b'][rs.A.shape[0]:].tobytes()))
+            else:
+                problem = backend._problem(rs.A, rs.b, rs.c, rs.key)
             pseudo = issubclass(self._Node, PseudoCostBranchNode)
             cut_params = None
             if self._kwargs.get('gomory_cuts', True):

@@ -342,6 +342,8 @@ struct Staging {
 #include "comm.hip.h"
 #include "spill_kernels.hip.h"
 #include "tree_engine.hip.h"
+#include "mir_kernels.hip.h"
+#include "mir_api.hip.h"
 
 extern "C" {
 
