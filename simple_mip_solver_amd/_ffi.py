@@ -440,6 +440,14 @@ _MIR_SIGNATURES = {
     'mipx_mir_separate_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _vp, _i, _vp, _i, _d, _d, _d] + [_vp] * 6),
 }
 MIR_SYMBOLS = list(_MIR_SIGNATURES)
+# ... and those of include/mipx_dualfn_batch.h (test scaffolding: the kernels of the dual function on a caller's
+# records), which mipx.h includes (tests/test_dualfn_batch_abi.py checks them against that header)
+_DUALFN_BATCH_SIGNATURES = {
+    'mipx_dualfn_record_batch': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    'mipx_dualfn_save_batch': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    'mipx_dualfn_eval_batch': (_i, [_vp] + [_i] * 4 + [_vp] * 6 + [_i, _vp, _i, _i] + [_vp] * 3),
+}
+DUALFN_BATCH_SYMBOLS = list(_DUALFN_BATCH_SIGNATURES)
 MIR_STATUS = {0: 'cut', 1: 'no_trial', 2: 'shallow', 3: 'dynamism', 4: 'skipped'}   # MIPX_MIR_* of the header
 # the defaults of the separation: divisor candidates per row (at most MIR_MAX_DIVISORS), the window of f0, the largest
 # ratio of a cut's coefficients
@@ -474,7 +482,7 @@ def lib():
                                       list(_CUBE_SIGNATURES.items()) + list(_COMPLETE_SIGNATURES.items()) +
                                       list(_LPDIVE_SIGNATURES.items()) + list(_FINISH_SIGNATURES.items()) +
                                       list(_CUTROUND_SIGNATURES.items()) + list(_CGLP_SCREEN_SIGNATURES.items()) +
-                                      list(_MIR_SIGNATURES.items())):
+                                      list(_MIR_SIGNATURES.items()) + list(_DUALFN_BATCH_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -900,6 +908,70 @@ def cut_round_generate_batch(problem, rnd, fill=0x5a):
         _ptr(out['k3_term']), _ptr(used))
     problem.ctx.check(rc, 'mipx_cut_round_generate_batch')
     out['chunks'], out['group'] = int(used[0]), int(used[1])
+    return out
+
+
+def _inout(rec, key, dtype, shape, fill):
+    """An in-and-out array of a scaffolding call: a copy of rec[key] where the caller sends one, else every byte `fill`."""
+    if rec.get(key) is None:
+        return _filled(shape, dtype, fill)
+    return np.array(rec[key], dtype=dtype, order='C').reshape(shape)
+
+
+def dualfn_record_batch(ctx, rec, fill=0x5a):
+    """Test scaffolding (mipx_dualfn_record_batch, include/mipx_dualfn_batch.h): dualfn_record on synthetic entries.
+    rec: a mapping with the scalars m, n, store_rows; A (m x n), c; src, lrow, dst (one per entry); y_src (rows of m),
+    l, u (rows of n); optionally store_y, store_t to start from.  Nothing of rec is written.  Returns dict of store_y
+    (store_rows x m) and store_t (whole arrays, every byte `fill` where the kernel wrote nothing and none was sent)."""
+    m, n, rows = (int(rec[k]) for k in ('m', 'n', 'store_rows'))
+    A, c = _arr(rec['A'], np.float64, (m, n)), _arr(rec['c'], np.float64, n)
+    src, lrow, dst = _arr(rec['src'], np.int32), _arr(rec['lrow'], np.int32), _arr(rec['dst'], np.int64)
+    count = len(src)
+    assert len(lrow) == count and len(dst) == count
+    y_src, l, u = _arr(rec['y_src'], np.float64, (-1, m)), _arr(rec['l'], np.float64, (-1, n)), _arr(rec['u'], np.float64, (-1, n))
+    assert len(l) == len(u)
+    out = dict(store_y=_inout(rec, 'store_y', np.float64, (rows, m), fill), store_t=_inout(rec, 'store_t', np.float64, (rows,), fill))
+    rc = lib().mipx_dualfn_record_batch(ctx._h, m, n, _ptr(A), _ptr(c), count, _ptr(src), _ptr(lrow), _ptr(dst), len(y_src),
+                                        _ptr(y_src), len(l), _ptr(l), _ptr(u), rows, _ptr(out['store_y']), _ptr(out['store_t']))
+    ctx.check(rc, 'mipx_dualfn_record_batch')
+    return out
+
+
+def dualfn_save_batch(ctx, rec, fill=0x5a):
+    """Test scaffolding (mipx_dualfn_save_batch): dualfn_save on synthetic entries.  rec: a mapping with the scalars n, nv,
+    out_rows; lrow, vpos, dst (one per entry); l, u (rows of n), vstat (rows of nv int8); optionally out_l, out_u, out_v to
+    start from.  Nothing of rec is written.  Returns dict of out_l, out_u (out_rows x n) and out_v (out_rows x nv), whole
+    arrays, every byte `fill` where the kernel wrote nothing and none was sent."""
+    n, nv, rows = (int(rec[k]) for k in ('n', 'nv', 'out_rows'))
+    lrow, vpos, dst = _arr(rec['lrow'], np.int32), _arr(rec['vpos'], np.int32), _arr(rec['dst'], np.int64)
+    count = len(lrow)
+    assert len(vpos) == count and len(dst) == count
+    l, u, vstat = _arr(rec['l'], np.float64, (-1, n)), _arr(rec['u'], np.float64, (-1, n)), _arr(rec['vstat'], np.int8, (-1, nv))
+    assert len(l) == len(u)
+    out = dict(out_l=_inout(rec, 'out_l', np.float64, (rows, n), fill), out_u=_inout(rec, 'out_u', np.float64, (rows, n), fill),
+               out_v=_inout(rec, 'out_v', np.int8, (rows, nv), fill))
+    rc = lib().mipx_dualfn_save_batch(ctx._h, n, nv, count, _ptr(lrow), _ptr(vpos), _ptr(dst), len(l), _ptr(l), _ptr(u), len(vstat),
+                                      _ptr(vstat), rows, _ptr(out['out_l']), _ptr(out['out_u']), _ptr(out['out_v']))
+    ctx.check(rc, 'mipx_dualfn_save_batch')
+    return out
+
+
+def dualfn_eval_batch(ctx, ev, k_tile=0, fill=0x5a):
+    """Test scaffolding (mipx_dualfn_eval_batch): dualfn_gemm then dualfn_lineage, tile by tile, on synthetic records.
+    ev: a mapping with Y (R x m), T (R), W (K x m), prec, order (R), lvl_off (nlvl + 1), leaf and the scalar bare.
+    k_tile > 0 caps the tile of right-hand sides.  Nothing of ev is written.  Returns dict of V_gemm, V_max (K x R) and
+    out (K), every byte `fill` where nothing was written."""
+    Y = np.ascontiguousarray(ev['Y'], dtype=np.float64)
+    R, m = Y.shape
+    T, W = _arr(ev['T'], np.float64, R), _arr(ev['W'], np.float64, (-1, m))
+    K = len(W)
+    prec, order, lvl_off = _arr(ev['prec'], np.int32, R), _arr(ev['order'], np.int32, R), _arr(ev['lvl_off'], np.int32)
+    leaf = _arr(ev['leaf'], np.int32)
+    out = dict(V_gemm=_filled((K, R), np.float64, fill), V_max=_filled((K, R), np.float64, fill), out=_filled(K, np.float64, fill))
+    rc = lib().mipx_dualfn_eval_batch(ctx._h, R, m, K, int(k_tile), _ptr(Y), _ptr(T), _ptr(W), _ptr(prec), _ptr(order), _ptr(lvl_off),
+                                      len(lvl_off) - 1, _ptr(leaf) if len(leaf) else None, len(leaf), int(ev['bare']),
+                                      _ptr(out['V_gemm']), _ptr(out['V_max']), _ptr(out['out']))
+    ctx.check(rc, 'mipx_dualfn_eval_batch')
     return out
 
 

@@ -58,6 +58,15 @@ int df_grow(mipx_tree *t, T **p, int64_t &have, int64_t need, size_t row, int64_
     return MIPX_OK;
 }
 
+// The launches of dualfn_record and dualfn_save, the grid from the count (count > 0): df_step, the end of
+// df_penalised and the entries of dualfn_batch_api.hip.h go through these two and through df_eval_tiles below.
+void enqueue_df_record(const mipx::DfRecordArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(mipx::dualfn_record, dim3((unsigned)((a.count + mipx::kDfRecRB - 1) / mipx::kDfRecRB)), dim3(mipx::kDfNT), 0, st, a);
+}
+void enqueue_df_save(const mipx::DfSaveArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(mipx::dualfn_save, dim3((unsigned)a.count), dim3(mipx::kDfNT), 0, st, a);
+}
+
 // The records of one host-finished step: recs = (output position, pool row, node id) of the nodes whose LP
 // ended optimal, infs = the same of those whose LP was infeasible, both in evaluation order.  Queued on cs
 // behind the step's children records (the dive children's rows hold their bounds by then).
@@ -115,7 +124,7 @@ int df_step(mipx_tree *t, StepBuf &S, hipStream_t cs, const std::vector<DfEntry>
         a.m = t->m; a.n = t->n; a.A = t->prob->dA; a.c = t->prob->dc; a.count = nr;
         a.src = (const int32_t *)S.df_d; a.lrow = a.src + rows; a.dst = (const int64_t *)(S.df_d + 8 * rows);
         a.y_src = S.df_y; a.l = t->pool_l; a.u = t->pool_u; a.store_y = df.d_y; a.store_t = df.d_t;
-        hipLaunchKernelGGL(mipx::dualfn_record, dim3((unsigned)((nr + mipx::kDfRecRB - 1) / mipx::kDfRecRB)), dim3(mipx::kDfNT), 0, cs, a);
+        enqueue_df_record(a, cs);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (ni > 0) {
@@ -124,7 +133,7 @@ int df_step(mipx_tree *t, StepBuf &S, hipStream_t cs, const std::vector<DfEntry>
         a.vpos = (const int32_t *)(S.df_d + 16 * rows); a.lrow = a.vpos + rows; a.dst = (const int64_t *)(S.df_d + 24 * rows);
         a.l = t->pool_l; a.u = t->pool_u; a.vstat = S.d_vout;
         a.out_l = df.d_il; a.out_u = df.d_iu; a.out_v = df.d_iv;
-        hipLaunchKernelGGL(mipx::dualfn_save, dim3((unsigned)ni), dim3(mipx::kDfNT), 0, cs, a);
+        enqueue_df_save(a, cs);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(S.df_e1, cs));
@@ -253,8 +262,7 @@ int df_penalised(mipx_tree *t, double M) {
                 a.src = (const int32_t *)(blk + o_src); a.lrow = a.src; a.dst = (const int64_t *)(blk + o_dst);
                 a.y_src = (const double *)(blk + o_y); a.l = (const double *)blk; a.u = (const double *)(blk + o_u);
                 a.store_y = df.d_y; a.store_t = df.d_t;
-                hipLaunchKernelGGL(mipx::dualfn_record, dim3((unsigned)((cnt + mipx::kDfRecRB - 1) / mipx::kDfRecRB)), dim3(mipx::kDfNT), 0,
-                                   ctx->stream, a);
+                enqueue_df_record(a, ctx->stream);
                 if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
                     rc = fail(ctx, MIPX_EHIP, "mipx_tree_dual_function: recording the penalised duals");
             }
@@ -314,7 +322,53 @@ int df_lineage(mipx_tree *t) {
     return MIPX_OK;
 }
 
-// f(w_k) for K right-hand sides, in tiles of the right-hand sides (V of a tile: R x Kt f64, at most 256 MB)
+// right-hand sides per tile: V of a tile is R x Kt f64, at most 256 MB; k_tile > 0 caps it further (the test entry)
+int df_tile(int64_t R, int K, int k_tile) {
+    const int64_t budget = ((int64_t)256 << 20) / 8;
+    int64_t Kt = std::max<int64_t>(1, std::min<int64_t>({(int64_t)K, (int64_t)1024, budget / R}));
+    if (k_tile > 0) Kt = std::min<int64_t>(Kt, k_tile);
+    return (int)Kt;
+}
+
+// The device arrays of an evaluation: R records (Y, T), their lineage, and room for one tile (W: Kt x m, V: Kt x R,
+// out: Kt, with Kt = df_tile(R, K, k_tile)).
+struct DfEvalDev {
+    int R = 0, m = 0;
+    const double *Y = nullptr, *T = nullptr;
+    const int32_t *prec = nullptr, *order = nullptr, *lvl_off = nullptr, *leaf = nullptr;
+    int nlvl = 0, nleaf = 0, bare = 0;
+    double *W = nullptr, *V = nullptr, *out = nullptr;
+};
+
+// The tile loop of an evaluation, queued on ctx->stream (the caller syncs): per tile the upload of its right-hand sides
+// from w (host, K x m), dualfn_gemm, dualfn_lineage and the download of its values into out (host, K).  v_gemm and v_max
+// (host, K x R, or null) take V as it is between the two kernels and after them: the test entry's, null in the engine.
+int df_eval_tiles(mipx_ctx *ctx, const DfEvalDev &d, int K, int k_tile, const double *w, double *out, double *v_gemm,
+                  double *v_max) {
+    const int Kt = df_tile(d.R, K, k_tile), m = d.m;
+    const size_t R = (size_t)d.R;
+    hipStream_t st = ctx->stream;
+    for (int k0 = 0; k0 < K; k0 += Kt) {
+        const int kt = std::min(Kt, K - k0);
+        HIP_TRY(ctx, hipMemcpyAsync(d.W, w + (size_t)k0 * m, (size_t)kt * m * 8, hipMemcpyHostToDevice, st));
+        mipx::DfGemmArgs g;
+        g.R = d.R; g.m = m; g.K = kt; g.Y = d.Y; g.T = d.T; g.W = d.W; g.V = d.V;
+        hipLaunchKernelGGL(mipx::dualfn_gemm, dim3((unsigned)((R + mipx::kDfTR - 1) / mipx::kDfTR), (unsigned)((kt + mipx::kDfTK - 1) / mipx::kDfTK)),
+                           dim3(mipx::kDfNT), 0, st, g);
+        HIP_TRY(ctx, hipGetLastError());
+        if (v_gemm) HIP_TRY(ctx, hipMemcpyAsync(v_gemm + (size_t)k0 * R, d.V, (size_t)kt * R * 8, hipMemcpyDeviceToHost, st));
+        mipx::DfLineageArgs a;
+        a.R = d.R; a.K = kt; a.V = d.V; a.prec = d.prec; a.order = d.order; a.lvl_off = d.lvl_off;
+        a.nlvl = d.nlvl; a.leaf = d.leaf; a.nleaf = d.nleaf; a.bare = d.bare; a.out = d.out;
+        hipLaunchKernelGGL(mipx::dualfn_lineage, dim3((unsigned)kt), dim3(mipx::kDfNT), 0, st, a);
+        HIP_TRY(ctx, hipGetLastError());
+        if (v_max) HIP_TRY(ctx, hipMemcpyAsync(v_max + (size_t)k0 * R, d.V, (size_t)kt * R * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(out + k0, d.out, (size_t)kt * 8, hipMemcpyDeviceToHost, st));
+    }
+    return MIPX_OK;
+}
+
+// f(w_k) for K right-hand sides, in tiles of the right-hand sides (df_tile)
 int df_evaluate(mipx_tree *t, int K, const double *w, double *out) {
     mipx_ctx *ctx = t->ctx;
     DualFn &df = t->df;
@@ -325,29 +379,17 @@ int df_evaluate(mipx_tree *t, int K, const double *w, double *out) {
                                                                         : -std::numeric_limits<double>::infinity();
         return MIPX_OK;
     }
-    const int64_t budget = ((int64_t)256 << 20) / 8;
-    const int Kt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)K, (int64_t)1024, budget / R}));
+    const int Kt = df_tile(R, K, 0);
     int64_t hv = (int64_t)df.vcap, hw = (int64_t)df.wcap, ho = (int64_t)df.ocap;
     if ((size_t)(R * Kt) > df.vcap) { if (df.d_V) (void)hipFree(df.d_V); df.d_V = nullptr; int rc = dmalloc(ctx, &df.d_V, (size_t)(R * Kt)); if (rc) return rc; hv = R * Kt; }
     if ((size_t)Kt * m > df.wcap) { if (df.d_W) (void)hipFree(df.d_W); df.d_W = nullptr; int rc = dmalloc(ctx, &df.d_W, (size_t)Kt * m); if (rc) return rc; hw = (int64_t)Kt * m; }
     if ((size_t)Kt > df.ocap) { if (df.d_out) (void)hipFree(df.d_out); df.d_out = nullptr; int rc = dmalloc(ctx, &df.d_out, (size_t)Kt); if (rc) return rc; ho = Kt; }
     df.vcap = (size_t)hv; df.wcap = (size_t)hw; df.ocap = (size_t)ho;
-    hipStream_t st = ctx->stream;
-    for (int k0 = 0; k0 < K; k0 += Kt) {
-        const int kt = std::min(Kt, K - k0);
-        HIP_TRY(ctx, hipMemcpyAsync(df.d_W, w + (size_t)k0 * m, (size_t)kt * m * 8, hipMemcpyHostToDevice, st));
-        mipx::DfGemmArgs g;
-        g.R = (int)R; g.m = m; g.K = kt; g.Y = df.d_y; g.T = df.d_t; g.W = df.d_W; g.V = df.d_V;
-        hipLaunchKernelGGL(mipx::dualfn_gemm, dim3((unsigned)((R + mipx::kDfTR - 1) / mipx::kDfTR), (unsigned)((kt + mipx::kDfTK - 1) / mipx::kDfTK)),
-                           dim3(mipx::kDfNT), 0, st, g);
-        HIP_TRY(ctx, hipGetLastError());
-        mipx::DfLineageArgs a;
-        a.R = (int)R; a.K = kt; a.V = df.d_V; a.prec = df.d_prec; a.order = df.d_order; a.lvl_off = df.d_lvl;
-        a.nlvl = df.nlvl; a.leaf = df.d_leaf; a.nleaf = df.nleaf; a.bare = df.bare; a.out = df.d_out;
-        hipLaunchKernelGGL(mipx::dualfn_lineage, dim3((unsigned)kt), dim3(mipx::kDfNT), 0, st, a);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(out + k0, df.d_out, (size_t)kt * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
+    DfEvalDev d;
+    d.R = (int)R; d.m = m; d.Y = df.d_y; d.T = df.d_t; d.prec = df.d_prec; d.order = df.d_order; d.lvl_off = df.d_lvl;
+    d.nlvl = df.nlvl; d.leaf = df.d_leaf; d.nleaf = df.nleaf; d.bare = df.bare; d.W = df.d_W; d.V = df.d_V; d.out = df.d_out;
+    int rc = df_eval_tiles(ctx, d, K, 0, w, out, nullptr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MIPX_OK;
 }

@@ -4686,6 +4686,7 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 }  // extern "C"
 
 #include "dualfn_api.hip.h"
+#include "dualfn_batch_api.hip.h"
 #include "treerec_api.hip.h"
 #include "cglp_api.hip.h"
 #include "restart_api.hip.h"
