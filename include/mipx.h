@@ -476,6 +476,64 @@ int mipx_comm_barrier(mipx_comm *c);
  * mipx_tree_global_stats adds the summed counters.
  */
 int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps);
+/*
+ * THE WIRE FORMAT OF A DONATION (a move (from, to, amount) of mipx_exchange_decide): one message of
+ * exactly `bytes` bytes, sent once by `from` and received once by `to`, little endian, every section
+ * 8-byte aligned.  Both ends compute amount, ctab and so bytes from the same gathered records; the
+ * message carries no size of its own.  With pad8(b) = (b + 7) / 8 * 8, n the columns, m the rows:
+ *
+ *   plain mode (no cut rounds): nvs = n + m
+ *     rowbytes = 16 n + pad8(nvs)
+ *     [0, amount x rowbytes)              amount ROWS: l (n f64), u (n f64), nvs int8 basis codes, pad
+ *     [meta_off = amount x rowbytes, ..)  META, 1 + 5 amount f64: count, then per record k < amount
+ *                                         dual bound, b_val, depth, b_idx, b_dir
+ *     bytes = meta_off + 8 (1 + 5 amount)
+ *
+ *   cut mode (every rank runs cut rounds with cut migration on, kc cut rows per node): nvs = n + m + kc
+ *     rowbytes = 16 n + pad8(nvs)
+ *     [0, amount x rowbytes)              the ROWS, as above
+ *     [refs_off = amount x rowbytes, ..)  LISTS, amount x (1 + kc) int32: ncut, then the refs of the
+ *                                         record's cut rows into the table, in list order; padded to 8
+ *     [tab_off = refs_off + pad8(4 amount (1 + kc)), ..)
+ *                                         TABLE: ctab x n f64 (pi, row after row), then ctab f64 (pi0)
+ *     [meta_off = tab_off + 8 ctab (n + 1), ..)
+ *                                         META, 1 + 6 amount + 1 f64: count, then per record k < amount
+ *                                         dual bound, b_val, depth, b_idx, b_dir, ncut; and as the last
+ *                                         f64 the table rows used (0 .. ctab)
+ *     bytes = meta_off + 8 (2 + 6 amount)
+ *
+ *   amount = min((open_from - open_to) / 2, 4096, room_to)   (records [2], [2], [11]; integer division)
+ *   ctab   = max(0, min(trunc([13] of the receiver's record), 16384, amount x kc))    (mipx_cutmig.h)
+ *
+ * count <= amount records are real: the donor gives every second of its best 2 x give open nodes with
+ * give = min(amount, (open nodes it has now - its frontier batch) / 2), never less than 0, and in cut mode
+ * keeps those whose rows no longer fit the table.  b_idx / b_dir / b_val: the branching that made the node
+ * (column, 0 down or 1 up, the LP value branched on: the bound of b_idx on that side is floor / ceil of
+ * b_val); depth >= 1 for every node but the root.  The numbers in META are f64 holding integers where the
+ * field is one.
+ * MEANINGFUL bytes are: META's count (and rows used), the META fields of records k < count, of ROWS
+ * k < count their l, u and the first n + m codes (cut mode: n + m + ncut), of LISTS k < count the ncut and
+ * the first ncut refs, of the TABLE the rows below `rows used`.  Everything else -- rows, lists and META
+ * fields at index count and above, the pad behind the codes, codes beyond n + m + ncut, refs beyond ncut,
+ * table rows at `rows used` and above -- is unspecified: a sender may leave anything there, a receiver must
+ * not read it.  A receiver refuses a message whose count is outside [0, amount] (cut mode also: rows used
+ * outside [0, ctab], an ncut outside [0, kc]) with MIPX_EHIP "corrupt migration message" before it changes
+ * anything, and one with a ref outside [0, rows used) with "corrupt cut lists".
+ *
+ * THE PSEUDO-COST MERGE.  A record's 4 n samples are cumulative since mipx_tree_set_comm: what this rank
+ * added to (sum_l, sum_r, times_l, times_r).  A rank never posts times below what it posted before (a tree
+ * whose steps the device finishes posts per entry the pair with the highest times it has held); the sums are
+ * >= 0 but need not grow with the times.  A tree whose steps the
+ * device finishes (max_batch > 1, no cut rounds) merges, at every applied exchange and in exchange order,
+ * per entry (variable, side) the others' increase since the HIGHEST times it has merged so far:
+ *   dt = times_others - times_merged, ds = sum_others - sum_merged;  only where dt > 0:
+ *   cost <- (cost * times + ds) / (times + dt), times <- times + dt, (sum, times)_merged <- (sum, times)_others
+ * (three roundings per merge; an entry whose times fall back and recover is therefore merged once).  Any
+ * other tree rebuilds the table at every applied exchange in sum form: times = base + others + own,
+ * cost = (sum_base + sum_others + sum_own) / times where times > 0, else 0 (both sums added left to
+ * right) -- base: cost * times of the table at mipx_tree_set_comm.  An entry exists where either side has
+ * times > 0.
+ */
 /* What every rank concludes from one gathered set of records -- a pure function of the records (no
  * GPU involved), exposed so that the decision logic can be tested across real processes on the CPU.
  * A record is mipx_exchange_record_len(n) doubles: [0] incumbent value, [1] dual bound of the shard,

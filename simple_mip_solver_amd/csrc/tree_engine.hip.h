@@ -557,6 +557,7 @@ struct mipx_tree {
     double *h_delta = nullptr, *d_delta = nullptr;   // exchange: the other ranks' new samples (4 staging slots)
     int delta_turn = 0;
     std::vector<double> pc_others_prev;
+    std::vector<double> pc_posted;  // own samples as last posted: per entry the (sum, times) with the highest times (x_fill_record)
     double *d_primal = nullptr;
     double primal_sent = std::numeric_limits<double>::infinity();   // what the device knows of the host's incumbent value
     bool fast_ok = false;           // steps are finished on the device where they file no probe request
@@ -2944,7 +2945,22 @@ void x_fill_record(mipx_tree *t) {
         r[15] = 1.0;
     }
     if (t->have_x) std::memcpy(r.data() + kRecHead, t->best_x.data(), n * 8);
-    std::memcpy(r.data() + kRecHead + n, t->pc_own.data(), 4 * n * 8);
+    if (t->rule == 1 && t->fast_ok) {
+        // A record never takes back a sample (mipx.h, the pseudo-cost merge).  Under the device finish with steps
+        // overlapped pc_own is a snapshot of the table version of the step finished last, and the samples of the
+        // nodes the host finished for the step before (deferred strong-branching probes) reach the version at the
+        // tail of the ring: for one step the snapshot lacks them.  Per entry the pair with the highest times is
+        // posted; the tail lineage holds every sample, so the posted pair is caught up with one step later.
+        if (t->pc_posted.size() != 4 * n) t->pc_posted.assign(4 * n, 0.0);
+        for (size_t e = 0; e < 2 * n; e++)
+            if (t->pc_own[2 * n + e] > t->pc_posted[2 * n + e]) {
+                t->pc_posted[e] = t->pc_own[e];
+                t->pc_posted[2 * n + e] = t->pc_own[2 * n + e];
+            }
+        std::memcpy(r.data() + kRecHead + n, t->pc_posted.data(), 4 * n * 8);
+    } else {
+        std::memcpy(r.data() + kRecHead + n, t->pc_own.data(), 4 * n * 8);
+    }
 }
 
 // A donation: `amount` node records from rank `from` to rank `to` (decided from the same records on
@@ -3403,12 +3419,23 @@ int x_apply(mipx_tree *t, const char *gathered, bool last) {
         // behind the finishes already there); the host's snapshot is merged the same way.
         if (t->pc_others_prev.size() != 4 * n) t->pc_others_prev.assign(4 * n, 0.0);
         double *hd = t->h_delta + (size_t)(t->delta_turn & 3) * 4 * n;
+        // Per entry the increase since the HIGHEST times merged so far, and only there does pc_others_prev
+        // advance: a peer's record whose times fall back for an exchange and recover (mipx.h, the pseudo-cost
+        // merge) is neither merged twice nor lost.  An entry that is not merged sends a zero delta.
         bool any = false;
-        for (size_t j = 0; j < 4 * n; j++) {
-            hd[j] = t->pc_others[j] - t->pc_others_prev[j];
-            any |= hd[j] != 0.0;
+        for (size_t e = 0; e < 2 * n; e++) {
+            const size_t js = e, jt = 2 * n + e;
+            const double dt = t->pc_others[jt] - t->pc_others_prev[jt];
+            if (dt > 0.0) {
+                hd[js] = t->pc_others[js] - t->pc_others_prev[js];
+                hd[jt] = dt;
+                t->pc_others_prev[js] = t->pc_others[js];
+                t->pc_others_prev[jt] = t->pc_others[jt];
+                any = true;
+            } else {
+                hd[js] = 0.0; hd[jt] = 0.0;
+            }
         }
-        t->pc_others_prev = t->pc_others;
         if (any) {
             for (size_t e = 0; e < 2 * n; e++) {
                 const size_t dir = e / n, var = e - dir * n;
@@ -4330,6 +4357,7 @@ int mipx_tree_set_comm(mipx_tree *t, mipx_comm *c, int every_steps) {
         HIP_TRY(t->ctx, hipStreamSynchronize(t->stf));
         HIP_TRY(t->ctx, hipMemset(tab_at(t, t->tab_tail).own, 0, 4 * n * 8));
         t->pc_others_prev.assign(4 * n, 0.0);
+        t->pc_posted.assign(4 * n, 0.0);
     }
     t->g_dual = tree_dual_bound(t);
     for (int k = 0; k < 4; k++) t->g_counts[k] = t->ramp[k];

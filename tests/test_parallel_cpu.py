@@ -16,24 +16,16 @@ import pytest
 
 from simple_mip_solver_amd import _ffi
 from simple_mip_solver_amd.parallel import env_ranks, global_gap, share_unique_id
+from tests.support.scripted_peer import make_record
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = float('inf')
 
 
-def record(n, primal=INF, dual=-INF, open_nodes=0, stop=0, counts=(0, 0, 0, 0), x=None, batch=8, samples=None,
-           room=1 << 30):
-    r = np.zeros(_ffi.exchange_record_len(n))
-    r[0], r[1], r[2], r[3] = primal, dual, open_nodes, stop
-    r[4:8] = counts
-    r[8] = 0.0 if x is None else 1.0
-    r[10] = batch
-    r[11] = room
-    r[12] = INF
-    if x is not None:
-        r[16:16 + n] = x
-    if samples is not None:
-        r[16 + n:] = samples
+def record(n, **fields):
+    """A record as a rank posts it (tests/support/scripted_peer.py builds all its fields from include/mipx.h)."""
+    r = make_record(n, **fields)
+    assert len(r) == _ffi.exchange_record_len(n)
     return r
 
 
