@@ -440,6 +440,12 @@ _MIR_SIGNATURES = {
     'mipx_mir_separate_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _vp, _i, _vp, _i, _d, _d, _d] + [_vp] * 6),
 }
 MIR_SYMBOLS = list(_MIR_SIGNATURES)
+# ... and that of include/mipx_cover.h (lifted knapsack cover cuts: batched separation from the rows), which mipx.h
+# includes (tests/test_cover_abi.py checks it against that header)
+_COVER_SIGNATURES = {
+    'mipx_cover_separate_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _vp, _i, _d] + [_vp] * 5),
+}
+COVER_SYMBOLS = list(_COVER_SIGNATURES)
 # ... and those of include/mipx_dualfn_batch.h (test scaffolding: the kernels of the dual function on a caller's
 # records), which mipx.h includes (tests/test_dualfn_batch_abi.py checks them against that header)
 _DUALFN_BATCH_SIGNATURES = {
@@ -449,6 +455,7 @@ _DUALFN_BATCH_SIGNATURES = {
 }
 DUALFN_BATCH_SYMBOLS = list(_DUALFN_BATCH_SIGNATURES)
 MIR_STATUS = {0: 'cut', 1: 'no_trial', 2: 'shallow', 3: 'dynamism', 4: 'skipped'}   # MIPX_MIR_* of the header
+COVER_STATUS = {0: 'cut', 1: 'no_cover', 2: 'shallow', 4: 'skipped'}   # MIPX_COVER_* of include/mipx_cover.h
 # the defaults of the separation: divisor candidates per row (at most MIR_MAX_DIVISORS), the window of f0, the largest
 # ratio of a cut's coefficients
 MIR_MAX_DIVISORS = 64
@@ -482,7 +489,8 @@ def lib():
                                       list(_CUBE_SIGNATURES.items()) + list(_COMPLETE_SIGNATURES.items()) +
                                       list(_LPDIVE_SIGNATURES.items()) + list(_FINISH_SIGNATURES.items()) +
                                       list(_CUTROUND_SIGNATURES.items()) + list(_CGLP_SCREEN_SIGNATURES.items()) +
-                                      list(_MIR_SIGNATURES.items()) + list(_DUALFN_BATCH_SIGNATURES.items())):
+                                      list(_MIR_SIGNATURES.items()) + list(_DUALFN_BATCH_SIGNATURES.items()) +
+                                      list(_COVER_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -1313,6 +1321,29 @@ class Problem:
         ms = self.ctx.last_kernel_ms() if B else 0.0
         return dict(pi=pi, pi0=pi0, efficacy=eff, delta=delta, sign=sign, status=status,
                     kernel_us=max(ms, 0.0) * 1e3)
+
+    def cover_separate_batch(self, x, l, u, integer_indices, rows=None, min_efficacy=1e-6):
+        """Lifted cover separation on host buffers (mipx_cover_separate_batch, include/mipx_cover.h): x, l, u
+        (batch, n) points and boxes, rows None (the m rows) or R distinct row indices shared by the points.  Returns
+        dict of pi (batch, R, n), pi0, efficacy, cover_size, status (COVER_STATUS codes; batch, R each) and kernel_us,
+        the device time of the kernel."""
+        n, m = self.n, self.m
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n)
+        B = x.shape[0]
+        l = np.ascontiguousarray(l, dtype=np.float64).reshape(-1, n)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, n)
+        assert l.shape[0] == B and u.shape[0] == B, 'x, l and u hold the same number of rows'
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        ro = _arr(rows, np.int32)
+        R = m if ro is None else len(ro)
+        pi = np.zeros((B, R, n)); pi0 = np.zeros((B, R)); eff = np.zeros((B, R))
+        size = np.zeros((B, R), np.int32); status = np.zeros((B, R), np.int32)
+        rc = lib().mipx_cover_separate_batch(self._h, B, _ptr(x), _ptr(l), _ptr(u), _ptr(ii), len(ii), _ptr(ro),
+                                             0 if ro is None else R, float(min_efficacy), _ptr(pi), _ptr(pi0), _ptr(eff),
+                                             _ptr(size), _ptr(status))
+        self.ctx.check(rc, 'mipx_cover_separate_batch')
+        ms = self.ctx.last_kernel_ms() if B else 0.0
+        return dict(pi=pi, pi0=pi0, efficacy=eff, cover_size=size, status=status, kernel_us=max(ms, 0.0) * 1e3)
 
     def reduced_cost_tighten_batch(self, l, u, y, integer_indices, cutoff, tol=RCFIX_TOL, dtol=RCFIX_DTOL, in_place=False):
         """Reduced-cost bound tightening on host buffers (mipx_reduced_cost_tighten_batch, include/mipx_rcfix.h):

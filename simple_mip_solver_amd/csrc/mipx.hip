@@ -344,6 +344,8 @@ struct Staging {
 #include "tree_engine.hip.h"
 #include "mir_kernels.hip.h"
 #include "mir_api.hip.h"
+#include "cover_kernels.hip.h"
+#include "cover_api.hip.h"
 
 extern "C" {
 

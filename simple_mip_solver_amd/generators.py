@@ -25,3 +25,21 @@ def random_dense_milp_arrays(num_vars, num_cons, density=1.0, max_obj_coeff=10,
     l = np.zeros(n)
     u = np.full(n, float(max_obj_coeff))
     return -A, -b, -c, l, u, list(range(n))
+
+
+def sparse_knapsack_milp_arrays(num_vars, num_cons, row_nonzeros, seed=0):
+    """Sparse binary multi-knapsack: max c'x, W x <= cap, x in {0, 1}^n, every row with `row_nonzeros` integer
+    weights in 5..30 on columns drawn without replacement, cap_i = floor(half the row's weight), c_j in 5..30; handed
+    over as min -c'x, -W x >= -cap.  A family on which rounding is strong: lifted cover cuts (include/mipx_cover.h)
+    close a large part of its root gap.  RNG: numpy Generator(PCG64(seed)), one row after the other, then c.
+
+    Return (A, b, c, l, u, integer_indices) already in `min c'x, Ax >= b` form."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n, m, k = int(num_vars), int(num_cons), int(row_nonzeros)
+    W = np.zeros((m, n))
+    for i in range(m):
+        cols = rng.choice(n, size=k, replace=False)
+        W[i, cols] = rng.integers(5, 31, k)
+    cap = np.floor(0.5 * W.sum(1))
+    c = rng.integers(5, 31, n).astype(np.float64)
+    return -W, -cap, -c, np.zeros(n), np.ones(n), list(range(n))

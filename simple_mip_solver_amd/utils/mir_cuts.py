@@ -1,6 +1,6 @@
 """Mixed-integer rounding cuts (include/mipx_mir.h): stand-alone separation on the GPU for users of lp_batch or of a
 loop of their own, the tableau rows of a basis as base rows, and the root cut loop behind
-BranchAndBound(root_cuts=...)."""
+BranchAndBound(root_cuts=...), which with cover=True also takes the lifted cover cuts of include/mipx_cover.h."""
 from math import cos, radians
 
 import numpy as np
@@ -119,6 +119,11 @@ class GpuRows:
         return dict(pi=r['pi'][0], pi0=r['pi0'][0], efficacy=r['efficacy'][0], status=r['status'][0],
                     kernel_us=r['kernel_us'])
 
+    def separate_cover(self, x, l, u, int_idx, rows, min_efficacy):
+        r = self.problem.cover_separate_batch(x[None], l[None], u[None], int_idx, rows, min_efficacy)
+        return dict(pi=r['pi'][0], pi0=r['pi0'][0], efficacy=r['efficacy'][0], status=r['status'][0],
+                    kernel_us=r['kernel_us'])
+
     def close(self):
         self.problem.close()
 
@@ -140,9 +145,20 @@ def select_cuts(pi, pi0, efficacy, status, taken, room, max_cuts, cos_parallel):
     return chosen
 
 
+def _chosen_places(sep, chosen):
+    """The candidate row each chosen cut was copied from: the first status-0 row with its coefficients (select_cuts
+    refuses a second copy as parallel)."""
+    places = []
+    for pi, pi0 in chosen:
+        places.append(next(k for k in range(len(sep['status'])) if sep['status'][k] == 0 and sep['pi0'][k] == pi0
+                           and np.array_equal(sep['pi'][k], pi)))
+    return places
+
+
 def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_rows=DEFAULT_ROOT_CUT_ROWS,
                   max_cuts_per_round=16, max_tableau_rows=64, parallel_cut_tolerance=tol.parallel_cut_tolerance,
-                  cutting_plane_progress_tolerance=tol.cutting_plane_progress_tolerance, make_rows=GpuRows, **params):
+                  cutting_plane_progress_tolerance=tol.cutting_plane_progress_tolerance, make_rows=GpuRows, cover=False,
+                  cover_min_efficacy=1e-6, **params):
     """Rounds of MIR separation at the root of min c x, A x >= b, l <= x <= u with the integer columns int_idx.
 
     Every round solves the LP over the model's rows and the cut rows alive (warm from the last basis, new rows basic),
@@ -153,7 +169,13 @@ def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_ro
     most max_rows cut rows are alive, and m + rows <= 1024.  make_rows(A, b, c) gives the object that solves and
     separates one row set (GpuRows; tests put a CPU restatement there); params go to the separation.
 
-    Returns dict(cuts=[(pi, pi0)], A, b (the model's rows and the cuts), vstat (the last basis or None), stats)."""
+    cover=True: every round also separates lifted cover cuts (include/mipx_cover.h) from the model's m rows, not from
+    the cut rows, in a second launch.  Their candidates stand behind the MIR candidates in the selection, so a tie in
+    efficacy goes to the MIR row.
+
+    Returns dict(cuts=[(pi, pi0)], A, b (the model's rows and the cuts), vstat (the last basis or None), stats), and
+    with cover=True also cover_stats (rounds, rows, found, skipped, selected, kept, kernel_us); `selected` and `kept`
+    of stats then count the MIR cuts alone, so the cuts returned are stats['kept'] + cover_stats['kept']."""
     A, b, c = np.asarray(A, np.float64), np.asarray(b, np.float64), np.asarray(c, np.float64)
     l, u = np.asarray(l, np.float64), np.asarray(u, np.float64)
     m0, n = A.shape
@@ -165,6 +187,8 @@ def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_ro
     cuts, vstat, prev = [], None, None
     stats = dict(rounds=0, base_rows=0, found=0, selected=0, kept=0, bound_before=None, bound_after=None, lp_pivots=0,
                  kernel_us=0.0)
+    cover_stats = dict(rounds=0, rows=0, found=0, skipped=0, selected=0, kept=0, kernel_us=0.0) if cover else None
+    from_cover = []   # one flag per cut alive: it came from the cover separation
 
     def rows_of(cuts):
         if not cuts:
@@ -196,6 +220,7 @@ def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_ro
                             and vstat[n + m0 + k] == 1)]
             if len(keep) < len(cuts):
                 cuts = [cuts[k] for k in keep]
+                from_cover = [from_cover[k] for k in keep]
                 vstat = np.concatenate([vstat[:n + m0], vstat[n + m0:][keep]])
                 Ak, bk = rows_of(cuts)
                 rows = None
@@ -220,17 +245,36 @@ def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_ro
         stats['base_rows'] += len(M)
         stats['found'] += int(np.sum(sep['status'] == 0))
         stats['kernel_us'] += sep.get('kernel_us', 0.0)
+        n_mir = len(sep['status'])
+        if cover:
+            cov = rows.separate_cover(x, l, u, ints, None if mk == m0 else np.arange(m0, dtype=np.int32), cover_min_efficacy)
+            cover_stats['rounds'] += 1
+            cover_stats['rows'] += m0
+            cover_stats['found'] += int(np.sum(cov['status'] == 0))
+            cover_stats['skipped'] += int(np.sum(cov['status'] == 4))
+            cover_stats['kernel_us'] += cov.get('kernel_us', 0.0)
+            sep = {key: np.concatenate([sep[key], cov[key]]) for key in ('pi', 'pi0', 'efficacy', 'status')}
         chosen = select_cuts(sep['pi'], sep['pi0'], sep['efficacy'], sep['status'], cuts, room, max_cuts_per_round, cos_par)
         if not chosen:
             break
-        stats['selected'] += len(chosen)
+        # which of the chosen are cover cuts: select_cuts copies the rows, so they are found again by their place
+        flags = [k >= n_mir for k in _chosen_places(sep, chosen)] if cover else [False] * len(chosen)
+        stats['selected'] += len(chosen) - sum(flags)
+        if cover:
+            cover_stats['selected'] += sum(flags)
+        from_cover = from_cover + flags
         cuts = cuts + chosen
         vstat = np.concatenate([vstat, np.ones(len(chosen), np.int8)])
     for rows in made:   # (the row sets of the rounds: their device buffers go now)
         if hasattr(rows, 'close'):
             rows.close()
-    stats['kept'] = len(cuts)
+    stats['kept'] = len(cuts) - sum(from_cover)
+    if cover:
+        cover_stats['kept'] = sum(from_cover)
     Ak, bk = rows_of(cuts)
     if vstat is not None and len(vstat) != n + Ak.shape[0]:
         vstat = None
-    return dict(cuts=cuts, A=np.ascontiguousarray(Ak), b=np.ascontiguousarray(bk), vstat=vstat, stats=stats)
+    out = dict(cuts=cuts, A=np.ascontiguousarray(Ak), b=np.ascontiguousarray(bk), vstat=vstat, stats=stats)
+    if cover:
+        out['cover_stats'] = cover_stats
+    return out
