@@ -1,5 +1,7 @@
 // complete_api.hip.h -- the C entries of include/mipx_complete.h (included at the end of tree_engine.hip.h, which holds
 // the launch and the per-step halves: comp_launch, and the option's parts of heur_step_launch and heur_step_collect).
+// The buffers behind the option's step block are a StepRing (tree_engine.hip.h): the set entry switches the option off,
+// grows the ring, and switches it on last.  The batch entry's prologue is the shared one of mipx.hip (check_int_idx, ...).
 
 extern "C" {
 
@@ -11,23 +13,19 @@ int mipx_complete_batch(mipx_problem *p, int batch, const double *x, const doubl
     if (batch < 0 || n_int < 0 || n_int > p->n || !(ctol >= 0.0) || !l || !u || (n_int && !int_idx) ||
         (batch && (!x || !x_out || !obj_out || !status_out || !pivots_out)))
         return fail(ctx, MIPX_EINVAL, "mipx_complete_batch: bad argument");
-    std::vector<uint8_t> seen((size_t)p->n, 0);
-    for (int k = 0; k < n_int; k++) {
-        if (int_idx[k] < 0 || int_idx[k] >= p->n || seen[(size_t)int_idx[k]])
-            return fail(ctx, MIPX_EINVAL, "mipx_complete_batch: int_idx out of range or repeated");
-        seen[(size_t)int_idx[k]] = 1;
-    }
+    std::vector<uint8_t> is_int;
+    if (int rc = check_int_idx(ctx, "mipx_complete_batch", int_idx, n_int, p->n, "int_idx out of range or repeated", &is_int)) return rc;
     if (p->m > mipx::kCompMax || p->n > mipx::kCompMax)
         return fail(ctx, MIPX_ETOOBIG, "mipx_complete_batch: more than 1024 rows or columns");
     const size_t B = (size_t)batch, nn = (size_t)p->n, nv = nn + (size_t)p->m;
+    // (its own pass, not check_bounds: the two refusals alternate column by column, and the first bad column decides)
     for (size_t e = 0; e < nn; e++) {
         if (!std::isfinite(l[e]) || u[e] != u[e] || u[e] == -std::numeric_limits<double>::infinity())
             return fail(ctx, MIPX_EINVAL, "mipx_complete_batch: a lower bound that is not finite, or an upper bound that is NaN or -inf");
-        if (seen[e] && !std::isfinite(u[e]))
+        if (is_int[e] && !std::isfinite(u[e]))
             return fail(ctx, MIPX_EINVAL, "mipx_complete_batch: an integer column whose upper bound is not finite");
     }
-    for (size_t e = 0; e < B * nn; e++)
-        if (!std::isfinite(x[e])) return fail(ctx, MIPX_EINVAL, "mipx_complete_batch: a point that is not finite");
+    if (int rc = check_points(ctx, "mipx_complete_batch", x, B * nn)) return rc;
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Staging S(ctx, "mipx_complete_batch");
@@ -73,18 +71,7 @@ int mipx_tree_set_completion(mipx_tree *t, int on) {
         cc.d_ws = nullptr;
         int rc = dmalloc(ctx, &cc.d_ws, mipx::CompWs(2 * cap, (size_t)t->prob->m, (size_t)t->n).bytes());
         if (rc) return rc;
-        for (int k = 0; k < 3; k++) {
-            if (cc.d_x[k]) (void)hipFree(cc.d_x[k]);
-            if (cc.d_out[k]) (void)hipFree(cc.d_out[k]);
-            if (cc.h_out[k]) (void)hipHostFree(cc.h_out[k]);
-            cc.d_x[k] = nullptr; cc.d_out[k] = nullptr; cc.h_out[k] = nullptr;
-            rc = dmalloc(ctx, &cc.d_x[k], 2 * cap * (size_t)t->n);
-            if (rc == MIPX_OK) rc = dmalloc(ctx, &cc.d_out[k], out_bytes);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&cc.h_out[k], out_bytes));
-            if (!cc.e0[k]) HIP_TRY(ctx, hipEventCreate(&cc.e0[k]));
-            if (!cc.e1[k]) HIP_TRY(ctx, hipEventCreate(&cc.e1[k]));
-        }
+        if ((rc = cc.ring.grow(ctx, out_bytes, 2 * cap * (size_t)t->n))) return rc;
         cc.cap = t->hr.cap;   // (laid out for cc.cap points per block: step_layout::CompOut)
     }
     if (t->n_int == t->n) cc.cap = std::max(cc.cap, t->hr.cap);   // (no continuous column: nothing is ever launched, no buffer is needed)

@@ -1,5 +1,7 @@
 // cube_api.hip.h -- the C entries of include/mipx_cube.h (included at the end of tree_engine.hip.h, which holds the
 // launch and the per-step halves: cube_launch, and the option's parts of heur_step_launch and heur_step_collect).
+// The buffers behind the option's step block are a StepRing (tree_engine.hip.h): the set entry switches the option off,
+// grows the ring, and switches it on last.  The batch entry's prologue is the shared one of mipx.hip (check_int_idx, ...).
 
 extern "C" {
 
@@ -13,20 +15,12 @@ int mipx_cube_search_batch(mipx_problem *p, int batch, const double *x, const do
         max_columns > MIPX_CUBE_MAX_COLUMNS || !l || !u || (n_int && !int_idx) ||
         (batch && (!x || !x_out || !obj_out || !status_out || !counts_out)))
         return fail(ctx, MIPX_EINVAL, "mipx_cube_search_batch: bad argument");
-    std::vector<uint8_t> seen((size_t)p->n, 0);
-    for (int k = 0; k < n_int; k++) {
-        if (int_idx[k] < 0 || int_idx[k] >= p->n || seen[(size_t)int_idx[k]])
-            return fail(ctx, MIPX_EINVAL, "mipx_cube_search_batch: int_idx out of range or repeated");
-        seen[(size_t)int_idx[k]] = 1;
-    }
+    if (int rc = check_int_idx(ctx, "mipx_cube_search_batch", int_idx, n_int, p->n)) return rc;
     if (p->m > mipx::kCubeMax || p->n > mipx::kCubeMax)
         return fail(ctx, MIPX_ETOOBIG, "mipx_cube_search_batch: more than 1024 rows or columns");
     const size_t B = (size_t)batch, nn = (size_t)p->n;
-    for (size_t e = 0; e < nn; e++)
-        if (!std::isfinite(l[e]) || u[e] != u[e] || u[e] == -std::numeric_limits<double>::infinity())
-            return fail(ctx, MIPX_EINVAL, "mipx_cube_search_batch: a lower bound that is not finite, or an upper bound that is NaN or -inf");
-    for (size_t e = 0; e < B * nn; e++)
-        if (!std::isfinite(x[e])) return fail(ctx, MIPX_EINVAL, "mipx_cube_search_batch: a point that is not finite");
+    if (int rc = check_bounds(ctx, "mipx_cube_search_batch", nullptr, l, u, nn)) return rc;
+    if (int rc = check_points(ctx, "mipx_cube_search_batch", x, B * nn)) return rc;
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Staging S(ctx, "mipx_cube_search_batch");
@@ -64,21 +58,10 @@ int mipx_tree_set_cube_search(mipx_tree *t, int max_columns) {
         return fail(ctx, MIPX_ETOOBIG, "mipx_tree_set_cube_search: more than 1024 rows or columns");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (t->hr.cap > cu.cap) {   // (the heuristic's step buffers grew or are new: nothing is in flight before the first step)
-        const size_t out_bytes = step_layout::CubeOut((size_t)t->hr.cap).bytes();
         cu.on = false;   // (until every block is there: a failure below leaves the option off and nothing to launch on)
         cu.cap = 0;
-        for (int k = 0; k < 3; k++) {
-            if (cu.d_x[k]) (void)hipFree(cu.d_x[k]);
-            if (cu.d_out[k]) (void)hipFree(cu.d_out[k]);
-            if (cu.h_out[k]) (void)hipHostFree(cu.h_out[k]);
-            cu.d_x[k] = nullptr; cu.d_out[k] = nullptr; cu.h_out[k] = nullptr;
-            int rc = dmalloc(ctx, &cu.d_x[k], (size_t)t->hr.cap * (size_t)t->n);
-            if (rc == MIPX_OK) rc = dmalloc(ctx, &cu.d_out[k], out_bytes);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&cu.h_out[k], out_bytes));
-            if (!cu.e0[k]) HIP_TRY(ctx, hipEventCreate(&cu.e0[k]));
-            if (!cu.e1[k]) HIP_TRY(ctx, hipEventCreate(&cu.e1[k]));
-        }
+        const int rc = cu.ring.grow(ctx, step_layout::CubeOut((size_t)t->hr.cap).bytes(), (size_t)t->hr.cap * (size_t)t->n);
+        if (rc) return rc;
         cu.cap = t->hr.cap;   // (laid out for cu.cap points: step_layout::CubeOut)
         cu.ws_columns = 0;    // (and the workspace with them)
     }

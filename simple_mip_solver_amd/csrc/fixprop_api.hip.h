@@ -1,5 +1,7 @@
 // fixprop_api.hip.h -- the C entries of include/mipx_fixprop.h (included at the end of tree_engine.hip.h, which holds
 // the launch and the per-step halves: fp_launch, and the dive's parts of heur_step_launch and heur_step_collect).
+// The buffers behind the option's step block are a StepRing (tree_engine.hip.h): the set entry switches the option off,
+// grows the ring, and switches it on last.  The batch entry's prologue is the shared one of mipx.hip (check_int_idx, ...).
 
 extern "C" {
 
@@ -12,20 +14,12 @@ int mipx_fix_propagate_batch(mipx_problem *p, int batch, const double *x, const 
     if (batch < 0 || n_int < 0 || n_int > p->n || !(tol >= 0.0) || max_rounds < 1 || max_tries < 0 || cutoff != cutoff || !l || !u ||
         (n_int && !int_idx) || (batch && (!x || !x_out || !obj_out || !status_out || !counts_out)))
         return fail(ctx, MIPX_EINVAL, "mipx_fix_propagate_batch: bad argument");
-    std::vector<uint8_t> seen((size_t)p->n, 0);
-    for (int k = 0; k < n_int; k++) {
-        if (int_idx[k] < 0 || int_idx[k] >= p->n || seen[(size_t)int_idx[k]])
-            return fail(ctx, MIPX_EINVAL, "mipx_fix_propagate_batch: int_idx out of range or repeated");
-        seen[(size_t)int_idx[k]] = 1;
-    }
+    if (int rc = check_int_idx(ctx, "mipx_fix_propagate_batch", int_idx, n_int, p->n)) return rc;
     if (p->m > mipx::kFpMax || p->n > mipx::kFpMax)
         return fail(ctx, MIPX_ETOOBIG, "mipx_fix_propagate_batch: more than 1024 rows or columns");
     const size_t B = (size_t)batch, nn = (size_t)p->n;
-    for (size_t e = 0; e < nn; e++)
-        if (!std::isfinite(l[e]) || u[e] != u[e] || u[e] == -std::numeric_limits<double>::infinity())
-            return fail(ctx, MIPX_EINVAL, "mipx_fix_propagate_batch: a lower bound that is not finite, or an upper bound that is NaN or -inf");
-    for (size_t e = 0; e < B * nn; e++)
-        if (!std::isfinite(x[e])) return fail(ctx, MIPX_EINVAL, "mipx_fix_propagate_batch: a point that is not finite");
+    if (int rc = check_bounds(ctx, "mipx_fix_propagate_batch", nullptr, l, u, nn)) return rc;
+    if (int rc = check_points(ctx, "mipx_fix_propagate_batch", x, B * nn)) return rc;
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Staging S(ctx, "mipx_fix_propagate_batch");
@@ -62,17 +56,10 @@ int mipx_tree_set_fix_propagate(mipx_tree *t, int max_rounds, int max_tries) {
         return fail(ctx, MIPX_EINVAL, "mipx_tree_set_fix_propagate: not with the weighted row repair (mipx_tree_set_weighted_repair(t, 0) first)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (t->hr.cap > fp.cap) {   // (the heuristic's step buffers grew or are new: nothing is in flight before the first step)
-        const size_t out_bytes = step_layout::FpOut((size_t)t->hr.cap).bytes();
-        for (int k = 0; k < 3; k++) {
-            if (fp.d_out[k]) (void)hipFree(fp.d_out[k]);
-            if (fp.h_out[k]) (void)hipHostFree(fp.h_out[k]);
-            fp.d_out[k] = nullptr; fp.h_out[k] = nullptr;
-            int rc = dmalloc(ctx, &fp.d_out[k], out_bytes);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&fp.h_out[k], out_bytes));
-            if (!fp.e0[k]) HIP_TRY(ctx, hipEventCreate(&fp.e0[k]));
-            if (!fp.e1[k]) HIP_TRY(ctx, hipEventCreate(&fp.e1[k]));
-        }
+        fp.on = false;   // (until every block is there: a failure below leaves the option off and nothing to launch on)
+        fp.cap = 0;
+        const int rc = fp.ring.grow(ctx, step_layout::FpOut((size_t)t->hr.cap).bytes(), 0);
+        if (rc) return rc;
         fp.cap = t->hr.cap;   // (laid out for fp.cap points: step_layout::FpOut)
     }
     fp.max_rounds = max_rounds;

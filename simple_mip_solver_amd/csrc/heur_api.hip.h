@@ -1,5 +1,7 @@
 // heur_api.hip.h -- the C entries of include/mipx_heur.h (included at the end of tree_engine.hip.h, which holds
 // the launch and the per-step halves: heur_launch, heur_step_launch, heur_step_collect).
+// The buffers behind the option's step block are a StepRing (tree_engine.hip.h): the set entry switches the option off,
+// grows the ring, and switches it on last.  The batch entry's prologue is the shared one of mipx.hip (check_int_idx, ...).
 
 extern "C" {
 
@@ -11,12 +13,7 @@ int mipx_round_repair_batch(mipx_problem *p, int batch, const double *x, const d
     if (batch < 0 || n_int < 0 || n_int > p->n || !(tol >= 0.0) || max_moves < 0 || !l || !u || (n_int && !int_idx) ||
         (batch && (!x || !x_out || !obj_out || !status_out || !moves_out)))
         return fail(ctx, MIPX_EINVAL, "mipx_round_repair_batch: bad argument");
-    std::vector<uint8_t> seen((size_t)p->n, 0);
-    for (int k = 0; k < n_int; k++) {
-        if (int_idx[k] < 0 || int_idx[k] >= p->n || seen[(size_t)int_idx[k]])
-            return fail(ctx, MIPX_EINVAL, "mipx_round_repair_batch: int_idx out of range or repeated");
-        seen[(size_t)int_idx[k]] = 1;
-    }
+    if (int rc = check_int_idx(ctx, "mipx_round_repair_batch", int_idx, n_int, p->n)) return rc;
     if (p->m > mipx::kHeurMax || p->n > mipx::kHeurMax)
         return fail(ctx, MIPX_ETOOBIG, "mipx_round_repair_batch: more than 1024 rows or columns");
     if (batch == 0) return MIPX_OK;
@@ -70,18 +67,10 @@ int mipx_tree_set_heuristic(mipx_tree *t, int points_per_step, int every_steps, 
     if (t->ld.on && P > t->ld.cap)
         return fail(ctx, MIPX_EINVAL, "mipx_tree_set_heuristic: more points than the LP dive was set for (mipx_tree_set_lpdive(t, 0, 0, 0) first)");
     if (P > hr.cap) {   // (set again with more points: the step buffers grow; nothing is in flight before the first step)
-        for (int k = 0; k < 3; k++) {
-            if (hr.d_x[k]) (void)hipFree(hr.d_x[k]);
-            if (hr.d_out[k]) (void)hipFree(hr.d_out[k]);
-            if (hr.h_out[k]) (void)hipHostFree(hr.h_out[k]);
-            hr.d_x[k] = nullptr; hr.d_out[k] = nullptr; hr.h_out[k] = nullptr;
-            const size_t out_bytes = step_layout::HeurOut((size_t)P).bytes();
-            int rc = dmalloc(ctx, &hr.d_x[k], (size_t)P * n) | dmalloc(ctx, &hr.d_out[k], out_bytes);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&hr.h_out[k], out_bytes));
-            if (!hr.e0[k]) HIP_TRY(ctx, hipEventCreate(&hr.e0[k]));
-            if (!hr.e1[k]) HIP_TRY(ctx, hipEventCreate(&hr.e1[k]));
-        }
+        hr.on = false;   // (until every block is there: a failure below leaves the option off and nothing to launch on)
+        hr.cap = 0;
+        const int rc = hr.ring.grow(ctx, step_layout::HeurOut((size_t)P).bytes(), (size_t)P * n);
+        if (rc) return rc;
         hr.cap = P;   // (the step buffers are laid out for hr.cap points: step_layout::HeurOut)
     }
     hr.points = P;

@@ -1,5 +1,7 @@
 // lpdive_api.hip.h -- the C entries of include/mipx_lpdive.h (included at the end of tree_engine.hip.h, which holds the
 // launch and the per-step halves: lpdive_launch, and the option's parts of heur_step_launch and heur_step_collect).
+// The buffers behind the option's step block are a StepRing (tree_engine.hip.h): the set entry switches the option off,
+// grows the ring, and switches it on last.  The batch entry's prologue is the shared one of mipx.hip (check_int_idx, ...).
 
 extern "C" {
 
@@ -18,18 +20,11 @@ int mipx_lpdive_batch(mipx_problem *p, int batch, const double *x, const double 
     if (rule != MIPX_LPDIVE_RULE_FRACTIONAL && rule != MIPX_LPDIVE_RULE_COEFFICIENT)
         return fail(ctx, MIPX_EINVAL, "mipx_lpdive_batch: the rule is 0 (fractional) or 1 (coefficient)");
     if (cutoff != cutoff) return fail(ctx, MIPX_EINVAL, "mipx_lpdive_batch: the cutoff is NaN");
-    std::vector<uint8_t> seen((size_t)p->n, 0);
-    for (int k = 0; k < n_int; k++) {
-        if (int_idx[k] < 0 || int_idx[k] >= p->n || seen[(size_t)int_idx[k]])
-            return fail(ctx, MIPX_EINVAL, "mipx_lpdive_batch: int_idx out of range or repeated");
-        seen[(size_t)int_idx[k]] = 1;
-    }
+    if (int rc = check_int_idx(ctx, "mipx_lpdive_batch", int_idx, n_int, p->n)) return rc;
     if (p->m > mipx::kLpdiveMax || p->n > mipx::kLpdiveMax)
         return fail(ctx, MIPX_ETOOBIG, "mipx_lpdive_batch: more than 1024 rows or columns");
     const size_t B = (size_t)batch, nn = (size_t)p->n, nv = nn + (size_t)p->m;
-    for (size_t e = 0; e < B * nn; e++)
-        if (!std::isfinite(l[e]) || u[e] != u[e] || u[e] == -std::numeric_limits<double>::infinity())
-            return fail(ctx, MIPX_EINVAL, "mipx_lpdive_batch: a lower bound that is not finite, or an upper bound that is NaN or -inf");
+    if (int rc = check_bounds(ctx, "mipx_lpdive_batch", nullptr, l, u, B * nn)) return rc;
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Staging S(ctx, "mipx_lpdive_batch");
@@ -95,18 +90,7 @@ int mipx_tree_set_lpdive(mipx_tree *t, int max_rounds, int every, int rule) {
         ld.d_ws = nullptr;
         int rc = dmalloc(ctx, &ld.d_ws, mipx::LpdiveWs(cap, (size_t)t->prob->m, (size_t)t->n).bytes());
         if (rc) return rc;
-        for (int k = 0; k < 3; k++) {
-            if (ld.d_x[k]) (void)hipFree(ld.d_x[k]);
-            if (ld.d_out[k]) (void)hipFree(ld.d_out[k]);
-            if (ld.h_out[k]) (void)hipHostFree(ld.h_out[k]);
-            ld.d_x[k] = nullptr; ld.d_out[k] = nullptr; ld.h_out[k] = nullptr;
-            rc = dmalloc(ctx, &ld.d_x[k], cap * (size_t)t->n);
-            if (rc == MIPX_OK) rc = dmalloc(ctx, &ld.d_out[k], out_bytes);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&ld.h_out[k], out_bytes));
-            if (!ld.e0[k]) HIP_TRY(ctx, hipEventCreate(&ld.e0[k]));
-            if (!ld.e1[k]) HIP_TRY(ctx, hipEventCreate(&ld.e1[k]));
-        }
+        if ((rc = ld.ring.grow(ctx, out_bytes, cap * (size_t)t->n))) return rc;
         ld.cap = t->hr.cap;
     }
     ld.max_rounds = max_rounds; ld.every = every; ld.rule = rule;

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "complete_kernels.hip.h"
+#include "step_layout.h"
 
 namespace mipx {
 
@@ -46,13 +47,23 @@ struct LpdiveWs {
     size_t bytes() const { return end; }
 };
 
-// What comes down with a step of the search, cap points: [obj] (f64) [status | rounds | fixings | flips | pivots] (i32).
+// What comes down with a step of the search, cap points: [obj] (f64) [status | rounds | fixings | flips | pivots] (i32);
+// view(base) as the layouts of step_layout.h have it (host-usable: no device code).
 struct LpdiveOut {
     size_t obj, status, rounds, fixings, flips, pivots, end;
     explicit LpdiveOut(size_t cap)
         : obj(0), status(8 * cap), rounds(status + 4 * cap), fixings(rounds + 4 * cap), flips(fixings + 4 * cap),
           pivots(flips + 4 * cap), end(pivots + 4 * cap) {}
     size_t bytes() const { return end; }
+    template <class Base> struct View {
+        step_layout::Like<double, Base> *obj;
+        step_layout::Like<int32_t, Base> *status, *rounds, *fixings, *flips, *pivots;
+    };
+    template <class Base> View<Base> view(Base *b) const {
+        using step_layout::at;
+        return {at<double>(b, obj), at<int32_t>(b, status), at<int32_t>(b, rounds), at<int32_t>(b, fixings),
+                at<int32_t>(b, flips), at<int32_t>(b, pivots)};
+    }
 };
 
 struct LpdiveArgs {

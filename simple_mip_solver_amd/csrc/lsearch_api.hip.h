@@ -1,6 +1,8 @@
 // lsearch_api.hip.h -- the C entries of include/mipx_lsearch.h (included at the end of tree_engine.hip.h, which
 // holds the launch and the per-step halves: ls_launch, and the local-search parts of heur_step_launch and
 // heur_step_collect).
+// The buffers behind the option's step block are a StepRing (tree_engine.hip.h): the set entry switches the option off,
+// grows the ring, and switches it on last.  The batch entry's prologue is the shared one of mipx.hip (check_int_idx, ...).
 
 extern "C" {
 
@@ -12,12 +14,7 @@ int mipx_pair_search_batch(mipx_problem *p, int batch, const double *x, const do
     if (batch < 0 || n_int < 0 || n_int > p->n || !(tol >= 0.0) || max_moves < 0 || !l || !u || (n_int && !int_idx) ||
         (batch && (!x || !x_out || !obj_out || !status_out || !moves_out)))
         return fail(ctx, MIPX_EINVAL, "mipx_pair_search_batch: bad argument");
-    std::vector<uint8_t> seen((size_t)p->n, 0);
-    for (int k = 0; k < n_int; k++) {
-        if (int_idx[k] < 0 || int_idx[k] >= p->n || seen[(size_t)int_idx[k]])
-            return fail(ctx, MIPX_EINVAL, "mipx_pair_search_batch: int_idx out of range or repeated");
-        seen[(size_t)int_idx[k]] = 1;
-    }
+    if (int rc = check_int_idx(ctx, "mipx_pair_search_batch", int_idx, n_int, p->n)) return rc;
     if (p->m > mipx::kLsMax || p->n > mipx::kLsMax)
         return fail(ctx, MIPX_ETOOBIG, "mipx_pair_search_batch: more than 1024 rows or columns");
     if (batch == 0) return MIPX_OK;
@@ -55,17 +52,10 @@ int mipx_tree_set_local_search(mipx_tree *t, int max_moves) {
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (t->hr.cap > ls.cap) {   // (the heuristic's step buffers grew or are new: nothing is in flight before the first step)
-        const size_t out_bytes = step_layout::LsOut((size_t)t->hr.cap).bytes();
-        for (int k = 0; k < 3; k++) {
-            if (ls.d_out[k]) (void)hipFree(ls.d_out[k]);
-            if (ls.h_out[k]) (void)hipHostFree(ls.h_out[k]);
-            ls.d_out[k] = nullptr; ls.h_out[k] = nullptr;
-            int rc = dmalloc(ctx, &ls.d_out[k], out_bytes / 4);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&ls.h_out[k], out_bytes));
-            if (!ls.e0[k]) HIP_TRY(ctx, hipEventCreate(&ls.e0[k]));
-            if (!ls.e1[k]) HIP_TRY(ctx, hipEventCreate(&ls.e1[k]));
-        }
+        ls.on = false;   // (until every block is there: a failure below leaves the option off and nothing to launch on)
+        ls.cap = 0;
+        const int rc = ls.ring.grow(ctx, step_layout::LsOut((size_t)t->hr.cap).bytes(), 0);
+        if (rc) return rc;
         ls.cap = t->hr.cap;   // (laid out for ls.cap points: step_layout::LsOut)
     }
     ls.max_moves = max_moves;

@@ -3,9 +3,11 @@
 // that computes requires a live HIP device.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <string>
 #include <vector>
@@ -335,6 +337,62 @@ struct Staging {
         return rc;
     }
 };
+
+// The host prologue the batch entries share, each part called where the entry checked before (an entry that refuses a
+// problem as too big before it scans the points still does).  A refusal's message is `who`, ": " and the tail.
+int refuse(mipx_ctx *ctx, const char *who, const char *tail) {
+    return fail(ctx, MIPX_EINVAL, (std::string(who) + ": " + tail).c_str());
+}
+
+// A list of `count` indices into 0 .. n - 1 without repeats: int_idx for every entry (mark, if given, comes back with a 1
+// at every listed index), and the cover separator's rows with a tail of their own.
+int check_int_idx(mipx_ctx *ctx, const char *who, const int32_t *int_idx, int n_int, int n,
+                  const char *tail = "int_idx out of range or repeated", std::vector<uint8_t> *mark = nullptr) {
+    std::vector<uint8_t> seen((size_t)n, 0);
+    for (int k = 0; k < n_int; k++) {
+        if (int_idx[k] < 0 || int_idx[k] >= n || seen[(size_t)int_idx[k]]) return refuse(ctx, who, tail);
+        seen[(size_t)int_idx[k]] = 1;
+    }
+    if (mark) mark->swap(seen);
+    return MIPX_OK;
+}
+
+// `count` entries of points: all finite.
+int check_points(mipx_ctx *ctx, const char *who, const double *x, size_t count) {
+    for (size_t e = 0; e < count; e++)
+        if (!std::isfinite(x[e])) return refuse(ctx, who, "a point that is not finite");
+    return MIPX_OK;
+}
+
+// `count` entries of bounds: a finite lower bound, an upper bound that is neither NaN nor -inf; with x (the separators,
+// whose points come one per box) the point's entry in the same pass, and the wording that names it.
+int check_bounds(mipx_ctx *ctx, const char *who, const double *x, const double *l, const double *u, size_t count) {
+    for (size_t e = 0; e < count; e++)
+        if ((x && !std::isfinite(x[e])) || !std::isfinite(l[e]) || u[e] != u[e] || u[e] == -std::numeric_limits<double>::infinity())
+            return refuse(ctx, who, x ? "a point or a lower bound that is not finite, or an upper bound that is NaN or -inf"
+                                      : "a lower bound that is not finite, or an upper bound that is NaN or -inf");
+    return MIPX_OK;
+}
+
+// The epilogue of the two separators: the context's event pair (made at the first use), `launch` -- one kernel, queued
+// on the context's stream -- between the two, the staging's finish, and the pair's time in ctx->last_kernel_ms (-1
+// where there is none).
+template <class Launch>
+int timed_launch_finish(Staging &S, int rc, Launch launch) {
+    mipx_ctx *ctx = S.ctx;
+    if (rc == MIPX_OK && !ctx->k0 && (hipEventCreate(&ctx->k0) != hipSuccess || hipEventCreate(&ctx->k1) != hipSuccess))
+        rc = fail(ctx, MIPX_EHIP, (std::string(S.who) + ": events").c_str());
+    if (rc == MIPX_OK) {
+        (void)hipEventRecord(ctx->k0, ctx->stream);
+        launch();
+        if (hipError_t e = hipGetLastError()) rc = fail(ctx, MIPX_EHIP, (std::string(S.who) + ": launch").c_str(), e);
+        else (void)hipEventRecord(ctx->k1, ctx->stream);
+    }
+    rc = S.finish(rc);
+    ctx->last_kernel_ms = -1.f;
+    if (rc == MIPX_OK && hipEventElapsedTime(&ctx->last_kernel_ms, ctx->k0, ctx->k1) != hipSuccess) ctx->last_kernel_ms = -1.f;
+    return rc;
+}
 
 }  // namespace
 

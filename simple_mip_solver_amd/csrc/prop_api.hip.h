@@ -1,5 +1,7 @@
 // prop_api.hip.h -- the C entries of include/mipx_prop.h (included at the end of tree_engine.hip.h, which holds
 // the launch and the per-step halves: prop_launch, prop_step_launch, prop_step_collect).
+// The buffers behind the option's step block are a StepRing (tree_engine.hip.h): the set entry switches the option off,
+// grows the ring, and switches it on last.  The batch entry's prologue is the shared one of mipx.hip (check_int_idx, ...).
 
 extern "C" {
 
@@ -11,18 +13,11 @@ int mipx_propagate_batch(mipx_problem *p, int batch, const double *l, const doub
     if (batch < 0 || n_int < 0 || n_int > p->n || !(tol >= 0.0) || max_rounds < 1 || cutoff != cutoff || (n_int && !int_idx) ||
         (batch && (!l || !u || !l_out || !u_out || !status_out || !changed_out || !rounds_out)))
         return fail(ctx, MIPX_EINVAL, "mipx_propagate_batch: bad argument");
-    std::vector<uint8_t> seen((size_t)p->n, 0);
-    for (int k = 0; k < n_int; k++) {
-        if (int_idx[k] < 0 || int_idx[k] >= p->n || seen[(size_t)int_idx[k]])
-            return fail(ctx, MIPX_EINVAL, "mipx_propagate_batch: int_idx out of range or repeated");
-        seen[(size_t)int_idx[k]] = 1;
-    }
+    if (int rc = check_int_idx(ctx, "mipx_propagate_batch", int_idx, n_int, p->n)) return rc;
     if (p->m > mipx::kPropMax || p->n > mipx::kPropMax)
         return fail(ctx, MIPX_ETOOBIG, "mipx_propagate_batch: more than 1024 rows or columns");
     const size_t B = (size_t)batch, nn = (size_t)p->n;
-    for (size_t e = 0; e < B * nn; e++)
-        if (!std::isfinite(l[e]) || u[e] != u[e] || u[e] == -std::numeric_limits<double>::infinity())
-            return fail(ctx, MIPX_EINVAL, "mipx_propagate_batch: a lower bound that is not finite, or an upper bound that is NaN or -inf");
+    if (int rc = check_bounds(ctx, "mipx_propagate_batch", nullptr, l, u, B * nn)) return rc;
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Staging S(ctx, "mipx_propagate_batch");
@@ -54,14 +49,9 @@ int mipx_tree_set_propagation(mipx_tree *t, int max_rounds, int use_cutoff) {
     PropState &pg = t->pg;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (pg.cap == 0) {
-        const size_t out_bytes = step_layout::PropOut((size_t)t->max_batch).bytes();
-        for (int k = 0; k < 3; k++) {
-            int rc = dmalloc(ctx, &pg.d_out[k], out_bytes / 4);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&pg.h_out[k], out_bytes));
-            HIP_TRY(ctx, hipEventCreate(&pg.e0[k]));
-            HIP_TRY(ctx, hipEventCreate(&pg.e1[k]));
-        }
+        pg.on = false;   // (until every block is there: a failure below leaves the option off and nothing to launch on)
+        const int rc = pg.ring.grow(ctx, step_layout::PropOut((size_t)t->max_batch).bytes(), 0);
+        if (rc) return rc;
         pg.cap = t->max_batch;   // (the step buffers are laid out for pg.cap nodes: step_layout::PropOut)
     }
     pg.max_rounds = max_rounds;

@@ -1,5 +1,6 @@
 // rcfix_api.hip.h -- the C entries of include/mipx_rcfix.h (included at the end of tree_engine.hip.h, which holds
 // the launch and the per-step parts: rc_launch, rc_step_stage, rc_level_launch, rc_step_collect).
+// The prologue is the shared one of mipx.hip (check_int_idx, check_bounds).
 
 extern "C" {
 
@@ -12,18 +13,11 @@ int mipx_reduced_cost_tighten_batch(mipx_problem *p, int batch, const double *l,
     if (batch < 0 || n_int < 0 || n_int > p->n || !(tol >= 0.0) || !(dtol >= 0.0) || cutoff != cutoff || (n_int && !int_idx) ||
         (batch && (!l || !u || (p->m > 0 && !y) || !l_out || !u_out || !z_out || !status_out || !changed_out)))
         return fail(ctx, MIPX_EINVAL, "mipx_reduced_cost_tighten_batch: bad argument");
-    std::vector<uint8_t> seen((size_t)p->n, 0);
-    for (int k = 0; k < n_int; k++) {
-        if (int_idx[k] < 0 || int_idx[k] >= p->n || seen[(size_t)int_idx[k]])
-            return fail(ctx, MIPX_EINVAL, "mipx_reduced_cost_tighten_batch: int_idx out of range or repeated");
-        seen[(size_t)int_idx[k]] = 1;
-    }
+    if (int rc = check_int_idx(ctx, "mipx_reduced_cost_tighten_batch", int_idx, n_int, p->n)) return rc;
     if (p->m > mipx::kRcMax || p->n > mipx::kRcMax)
         return fail(ctx, MIPX_ETOOBIG, "mipx_reduced_cost_tighten_batch: more than 1024 rows or columns");
     const size_t B = (size_t)batch, nn = (size_t)p->n, mm = (size_t)p->m;
-    for (size_t e = 0; e < B * nn; e++)
-        if (!std::isfinite(l[e]) || u[e] != u[e] || u[e] == -std::numeric_limits<double>::infinity())
-            return fail(ctx, MIPX_EINVAL, "mipx_reduced_cost_tighten_batch: a lower bound that is not finite, or an upper bound that is NaN or -inf");
+    if (int rc = check_bounds(ctx, "mipx_reduced_cost_tighten_batch", nullptr, l, u, B * nn)) return rc;
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Staging S(ctx, "mipx_reduced_cost_tighten_batch");

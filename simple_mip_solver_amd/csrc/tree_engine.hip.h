@@ -391,6 +391,24 @@ struct RestartRec {
     double seed_us = 0.0;             // device time of restart_seed
 };
 
+// What stands behind a step option's packed block, per step buffer: the block on the device, its pinned mirror,
+// optionally a block of points, and the event pair around the option's launches.  A plain struct that mipx_tree_destroy
+// releases like everything else of the tree; the members are defined beside dmalloc and tree_d2h.  It knows nothing of
+// an option's cap or on: the mipx_tree_set_* entries switch the option off, grow, and switch it on last.
+namespace {
+struct StepRing {
+    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    double *d_x[3] = {nullptr, nullptr, nullptr};   // (stays null where the option has no points of its own)
+    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    int grow(mipx_ctx *ctx, size_t out_bytes, size_t x_doubles);   // new blocks for all three buffers, or none at all
+    void drop();      // the blocks (grow and release use it)
+    void release();   // the blocks and the events
+    int begin(mipx_ctx *ctx, int bi, hipStream_t st);   // e0 of buffer bi, in front of the option's launches on st
+    int end(mipx_ctx *ctx, int bi, hipStream_t st);     // e1, behind them
+    int fetch(mipx_tree *t, int bi, size_t bytes, double &us);   // the block to its mirror; the pair's time onto us
+};
+}  // namespace
+
 // Primal heuristic (include/mipx_heur.h): the option's parameters, the root's bounds on the device, and per step
 // buffer the rounded points and what comes down with each step (step_layout::HeurOut).
 struct HeurState {
@@ -399,9 +417,7 @@ struct HeurState {
     int cap = 0;                     // points the step buffers are laid out for
     double tol = 1e-9;
     double *d_lu = nullptr;          // [root l | root u]
-    double *d_x[3] = {nullptr, nullptr, nullptr};
-    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    StepRing ring;                   // (with the rounded points)
     int64_t tried = 0, feasible = 0, stuck = 0, capped = 0, repair = 0, lift = 0, installed = 0;
     double us = 0.0;                 // device time of heur_round_repair
 };
@@ -412,8 +428,7 @@ struct LsState {
     bool on = false;
     int max_moves = 0;
     int cap = 0;                     // points the step buffers are laid out for (the heuristic's cap)
-    int32_t *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    StepRing ring;
     int64_t run = 0, improved = 0, singles = 0, pairs = 0, capped = 0, installed = 0;
     double us = 0.0;                 // device time of ls_pair_search
 };
@@ -424,8 +439,7 @@ struct FpState {
     bool on = false;
     int max_rounds = 0, max_tries = 0;
     int cap = 0;                     // points the step buffers are laid out for (the heuristic's cap)
-    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    StepRing ring;
     int64_t tried = 0, feasible = 0, stuck = 0, capped = 0, fixings = 0, tries = 0, installed = 0;
     double us = 0.0;                 // device time of fixprop_dive and of the lift behind it
 };
@@ -436,8 +450,7 @@ struct WrState {
     bool on = false;
     int max_steps = 0;
     int cap = 0;                     // points the step buffers are laid out for (the heuristic's cap)
-    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    StepRing ring;
     int64_t tried = 0, feasible = 0, capped = 0, moves = 0, bumps = 0, installed = 0;
     double us = 0.0;                 // device time of wrepair_steps and of the lift behind it
 };
@@ -450,9 +463,7 @@ struct CubeState {
     int max_columns = 0;
     int cap = 0, ws_columns = 0;     // points the step buffers are laid out for (the heuristic's cap); K the workspace is for
     char *d_ws = nullptr;
-    double *d_x[3] = {nullptr, nullptr, nullptr};
-    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    StepRing ring;                   // (with the option's points)
     int64_t tried = 0, found = 0, none = 0, columns = 0, at_cap = 0, installed = 0;
     double us = 0.0;                 // device time of the three kernels and of the lift behind them
 };
@@ -466,9 +477,7 @@ struct CompState {
     double ctol = 1e-6;
     int cap = 0;                     // points per block the step buffers are laid out for (the heuristic's cap)
     char *d_ws = nullptr;
-    double *d_x[3] = {nullptr, nullptr, nullptr};
-    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    StepRing ring;                   // (with the option's points)
     int64_t tried = 0, completed = 0, infeasible = 0, failed = 0, rescued = 0, installed = 0, pivots = 0;
     double us = 0.0;                 // device time of the two kernels and the LP launch between them
 };
@@ -482,9 +491,7 @@ struct LpdiveState {
     int cap = 0;                     // points the buffers are laid out for (the heuristic's cap)
     int32_t *d_locks = nullptr;
     char *d_ws = nullptr;
-    double *d_x[3] = {nullptr, nullptr, nullptr};
-    char *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    StepRing ring;                   // (with the option's points)
     int64_t tried = 0, feasible = 0, infeasible = 0, failed = 0, moves = 0, installed = 0, pivots = 0;
     double us = 0.0;                 // device time of the dive's kernels and the LP launches between them
 };
@@ -503,8 +510,7 @@ struct PropState {
     int max_rounds = 0, use_cutoff = 1;
     int cap = 0;                     // nodes the step buffers are laid out for (the tree's max_batch)
     double tol = 1e-6;
-    int32_t *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t e0[3] = {nullptr, nullptr, nullptr}, e1[3] = {nullptr, nullptr, nullptr};
+    StepRing ring;
     int64_t nodes = 0, tightened = 0, infeasible = 0, changed = 0, rounds = 0, capped = 0;
     double us = 0.0;                 // device time of prop_bounds
 };
@@ -677,6 +683,55 @@ int dmalloc(mipx_ctx *ctx, T **p, size_t count) {
     return MIPX_OK;
 }
 
+// The blocks of every buffer, null-safe; the events stay.
+void StepRing::drop() {
+    for (int k = 0; k < 3; k++) {
+        if (d_x[k]) (void)hipFree(d_x[k]);
+        if (d_out[k]) (void)hipFree(d_out[k]);
+        if (h_out[k]) (void)hipHostFree(h_out[k]);
+        d_x[k] = nullptr; d_out[k] = nullptr; h_out[k] = nullptr;
+    }
+}
+
+// The old blocks go first, then all three buffers are made anew (out_bytes each on the device and pinned, x_doubles
+// doubles of points where that is not 0) with the events that are not there yet.  A failure frees what was made: the
+// ring then holds no block at all, and the caller's option is off with nothing to launch on.
+int StepRing::grow(mipx_ctx *ctx, size_t out_bytes, size_t x_doubles) {
+    const auto make = [&](int k) -> int {
+        int rc = x_doubles ? dmalloc(ctx, &d_x[k], x_doubles) : MIPX_OK;
+        if (rc == MIPX_OK) rc = dmalloc(ctx, &d_out[k], out_bytes);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipHostMalloc((void **)&h_out[k], out_bytes));
+        if (!e0[k]) HIP_TRY(ctx, hipEventCreate(&e0[k]));
+        if (!e1[k]) HIP_TRY(ctx, hipEventCreate(&e1[k]));
+        return MIPX_OK;
+    };
+    drop();
+    int rc = MIPX_OK;
+    for (int k = 0; k < 3 && rc == MIPX_OK; k++) rc = make(k);
+    if (rc) drop();
+    return rc;
+}
+
+void StepRing::release() {
+    drop();
+    for (int k = 0; k < 3; k++) {
+        if (e0[k]) (void)hipEventDestroy(e0[k]);
+        if (e1[k]) (void)hipEventDestroy(e1[k]);
+        e0[k] = nullptr; e1[k] = nullptr;
+    }
+}
+
+int StepRing::begin(mipx_ctx *ctx, int bi, hipStream_t st) {
+    HIP_TRY(ctx, hipEventRecord(e0[bi], st));
+    return MIPX_OK;
+}
+
+int StepRing::end(mipx_ctx *ctx, int bi, hipStream_t st) {
+    HIP_TRY(ctx, hipEventRecord(e1[bi], st));
+    return MIPX_OK;
+}
+
 double tree_open_min(mipx_tree *t) {
     const double inf = std::numeric_limits<double>::infinity();
     if (t->use_bq) return t->bq.empty() ? inf : t->bq.min_key();
@@ -807,6 +862,14 @@ int launch_lp(mipx_tree *t, int batch, const double *l, const double *u, const i
 int tree_d2h(mipx_tree *t, void *dst, const void *src, size_t bytes) {
     HIP_TRY(t->ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, t->st2));
     HIP_TRY(t->ctx, hipStreamSynchronize(t->st2));
+    return MIPX_OK;
+}
+
+int StepRing::fetch(mipx_tree *t, int bi, size_t bytes, double &us) {
+    const int rc = tree_d2h(t, h_out[bi], d_out[bi], bytes);
+    if (rc) return rc;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e0[bi], e1[bi]) == hipSuccess) us += 1000.0 * ms;
     return MIPX_OK;
 }
 
@@ -1037,85 +1100,85 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
     mipx_ctx *ctx = t->ctx;
     hipStream_t st = ctx->stream;
     const int bi = (int)(&S - t->buf), P = std::min(S.B, hr.points);
-    const auto o = step_layout::HeurOut((size_t)hr.cap).view(hr.d_out[bi]);
-    HIP_TRY(ctx, hipEventRecord(hr.e0[bi], st));
+    const auto o = step_layout::HeurOut((size_t)hr.cap).view(hr.ring.d_out[bi]);
+    if (int e = hr.ring.begin(ctx, bi, st)) return e;
     const int rc = heur_launch(t->prob, st, P, S.d_x, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
-                               nullptr, S.d.status, hr.d_x[bi], o.obj, o.status, o.moves);
+                               nullptr, S.d.status, hr.ring.d_x[bi], o.obj, o.status, o.moves);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(hr.e1[bi], st));
+    if (int e = hr.ring.end(ctx, bi, st)) return e;
     S.heur_n = P;
     S.ls_n = 0;
     S.fp_n = 0;
     FpState &fp = t->fp;
-    const auto fo = step_layout::FpOut((size_t)(fp.on ? fp.cap : 0)).view(fp.on ? fp.d_out[bi] : nullptr);
+    const auto fo = step_layout::FpOut((size_t)(fp.on ? fp.cap : 0)).view(fp.on ? fp.ring.d_out[bi] : nullptr);
     if (fp.on) {
         // the same LP points, gated by the heuristic's status; a dive point lands in the heuristic's slot of hr.d_x, its
         // objective and the lifted one in the dive's own block (a point the lift skips has its objective there zeroed)
-        HIP_TRY(ctx, hipEventRecord(fp.e0[bi], st));
+        if (int e = fp.ring.begin(ctx, bi, st)) return e;
         int frc = fp_launch(t->prob, st, P, S.d_x, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, tree_cutoff(t), hr.tol,
-                            fp.max_rounds, fp.max_tries, nullptr, o.status, hr.d_x[bi], fo.obj, fo.status, fo.counts);
+                            fp.max_rounds, fp.max_tries, nullptr, o.status, hr.ring.d_x[bi], fo.obj, fo.status, fo.counts);
         if (frc) return frc;
-        frc = heur_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
-                          nullptr, fo.status, hr.d_x[bi], fo.obj, fo.lift_status, fo.lift_moves);
+        frc = heur_launch(t->prob, st, P, hr.ring.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
+                          nullptr, fo.status, hr.ring.d_x[bi], fo.obj, fo.lift_status, fo.lift_moves);
         if (frc) return frc;
-        HIP_TRY(ctx, hipEventRecord(fp.e1[bi], st));
+        if (int e = fp.ring.end(ctx, bi, st)) return e;
         S.fp_n = P;
     }
     S.wr_n = 0;
     WrState &wr = t->wr;
-    const auto wo = step_layout::WrOut((size_t)(wr.on ? wr.cap : 0)).view(wr.on ? wr.d_out[bi] : nullptr);
+    const auto wo = step_layout::WrOut((size_t)(wr.on ? wr.cap : 0)).view(wr.on ? wr.ring.d_out[bi] : nullptr);
     if (wr.on) {
         // the dive's place, to the letter: the same LP points, gated by the heuristic's status; a repaired point lands in
         // the heuristic's slot of hr.d_x, its objective and the lifted one in this option's own block
-        HIP_TRY(ctx, hipEventRecord(wr.e0[bi], st));
+        if (int e = wr.ring.begin(ctx, bi, st)) return e;
         int wrc = wr_launch(t->prob, st, P, S.d_x, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, wr.max_steps,
-                            nullptr, o.status, true, hr.d_x[bi], wo.obj, wo.status, wo.counts);
+                            nullptr, o.status, true, hr.ring.d_x[bi], wo.obj, wo.status, wo.counts);
         if (wrc) return wrc;
-        wrc = heur_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
-                          nullptr, wo.status, hr.d_x[bi], wo.obj, wo.lift_status, wo.lift_moves);
+        wrc = heur_launch(t->prob, st, P, hr.ring.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
+                          nullptr, wo.status, hr.ring.d_x[bi], wo.obj, wo.lift_status, wo.lift_moves);
         if (wrc) return wrc;
-        HIP_TRY(ctx, hipEventRecord(wr.e1[bi], st));
+        if (int e = wr.ring.end(ctx, bi, st)) return e;
         S.wr_n = P;
     }
     S.cube_n = 0;
     CubeState &cu = t->cu;
-    const auto co = step_layout::CubeOut((size_t)(cu.on ? cu.cap : 0)).view(cu.on ? cu.d_out[bi] : nullptr);
+    const auto co = step_layout::CubeOut((size_t)(cu.on ? cu.cap : 0)).view(cu.on ? cu.ring.d_out[bi] : nullptr);
     if (cu.on) {
         // the LP points again, gated by the node LP's status as the heuristic is; a FOUND point goes through the heuristic
         // in place (rounding an integral point changes nothing and its repair is empty: the lift), gated by the cube's status
-        HIP_TRY(ctx, hipEventRecord(cu.e0[bi], st));
+        if (int e = cu.ring.begin(ctx, bi, st)) return e;
         int crc = cube_launch(t->prob, st, P, S.d_x, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, tree_cutoff(t), hr.tol,
-                              mipx::kVarEps, cu.max_columns, nullptr, S.d.status, cu.d_ws, cu.d_x[bi], co.obj, co.status, co.counts);
+                              mipx::kVarEps, cu.max_columns, nullptr, S.d.status, cu.d_ws, cu.ring.d_x[bi], co.obj, co.status, co.counts);
         if (crc) return crc;
-        crc = heur_launch(t->prob, st, P, cu.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
-                          nullptr, co.status, cu.d_x[bi], co.obj, co.lift_status, co.lift_moves);
+        crc = heur_launch(t->prob, st, P, cu.ring.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, hr.max_moves,
+                          nullptr, co.status, cu.ring.d_x[bi], co.obj, co.lift_status, co.lift_moves);
         if (crc) return crc;
-        HIP_TRY(ctx, hipEventRecord(cu.e1[bi], st));
+        if (int e = cu.ring.end(ctx, bi, st)) return e;
         S.cube_n = P;
     }
     LsState &ls = t->ls;
     if (ls.on) {
-        const auto lo = step_layout::LsOut((size_t)ls.cap).view(ls.d_out[bi]);
-        HIP_TRY(ctx, hipEventRecord(ls.e0[bi], st));
-        const int lrc = ls_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, ls.max_moves,
-                                  nullptr, o.status, hr.d_x[bi], o.obj, lo.status, lo.moves);
+        const auto lo = step_layout::LsOut((size_t)ls.cap).view(ls.ring.d_out[bi]);
+        if (int e = ls.ring.begin(ctx, bi, st)) return e;
+        const int lrc = ls_launch(t->prob, st, P, hr.ring.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol, ls.max_moves,
+                                  nullptr, o.status, hr.ring.d_x[bi], o.obj, lo.status, lo.moves);
         if (lrc) return lrc;
         if (fp.on) {   // ... and the lifted dive points, whose objectives and counts are in the dive's block
-            const int drc = ls_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
-                                      ls.max_moves, nullptr, fo.lift_status, hr.d_x[bi], fo.obj, fo.ls_status, fo.ls_moves);
+            const int drc = ls_launch(t->prob, st, P, hr.ring.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
+                                      ls.max_moves, nullptr, fo.lift_status, hr.ring.d_x[bi], fo.obj, fo.ls_status, fo.ls_moves);
             if (drc) return drc;
         }
         if (wr.on) {   // ... or the lifted points of the weighted repair, in its block
-            const int wrc = ls_launch(t->prob, st, P, hr.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
-                                      ls.max_moves, nullptr, wo.lift_status, hr.d_x[bi], wo.obj, wo.ls_status, wo.ls_moves);
+            const int wrc = ls_launch(t->prob, st, P, hr.ring.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
+                                      ls.max_moves, nullptr, wo.lift_status, hr.ring.d_x[bi], wo.obj, wo.ls_status, wo.ls_moves);
             if (wrc) return wrc;
         }
         if (cu.on) {   // ... and the lifted cube points, in their own block
-            const int crc = ls_launch(t->prob, st, P, cu.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
-                                      ls.max_moves, nullptr, co.lift_status, cu.d_x[bi], co.obj, co.ls_status, co.ls_moves);
+            const int crc = ls_launch(t->prob, st, P, cu.ring.d_x[bi], hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, hr.tol,
+                                      ls.max_moves, nullptr, co.lift_status, cu.ring.d_x[bi], co.obj, co.ls_status, co.ls_moves);
             if (crc) return crc;
         }
-        HIP_TRY(ctx, hipEventRecord(ls.e1[bi], st));
+        if (int e = ls.ring.end(ctx, bi, st)) return e;
         S.ls_n = P;
     }
     // completion: behind the last stage of every block, the heuristic's slots (its own points and those of the dive or
@@ -1126,14 +1189,14 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
     S.comp_cube = false;
     CompState &cc = t->cc;
     if (cc.on && t->n_int < t->n) {
-        const auto qo = step_layout::CompOut((size_t)cc.cap).view(cc.d_out[bi]);
-        const CompSrc src[2] = {{hr.d_x[bi], nullptr, o.status, false, S.d_vout, P},
-                                {cu.on ? cu.d_x[bi] : nullptr, nullptr, co.status, true, S.d_vout, cu.on ? P : 0}};
-        HIP_TRY(ctx, hipEventRecord(cc.e0[bi], st));
+        const auto qo = step_layout::CompOut((size_t)cc.cap).view(cc.ring.d_out[bi]);
+        const CompSrc src[2] = {{hr.ring.d_x[bi], nullptr, o.status, false, S.d_vout, P},
+                                {cu.on ? cu.ring.d_x[bi] : nullptr, nullptr, co.status, true, S.d_vout, cu.on ? P : 0}};
+        if (int e = cc.ring.begin(ctx, bi, st)) return e;
         const int qrc = comp_launch(t->prob, st, src, 2, hr.d_lu, hr.d_lu + t->n, t->d_int_idx, t->n_int, cc.ctol, cc.d_ws,
-                                    cc.d_x[bi], qo.obj, qo.status, qo.pivots);
+                                    cc.ring.d_x[bi], qo.obj, qo.status, qo.pivots);
         if (qrc) return qrc;
-        HIP_TRY(ctx, hipEventRecord(cc.e1[bi], st));
+        if (int e = cc.ring.end(ctx, bi, st)) return e;
         S.comp_n = P;
         S.comp_cube = cu.on;
     }
@@ -1143,19 +1206,29 @@ int heur_step_launch(mipx_tree *t, StepBuf &S) {
     S.lpdive_n = 0;
     LpdiveState &ld = t->ld;
     if (ld.on && (!(t->primal < std::numeric_limits<double>::infinity()) || (ld.every > 0 && t->steps % ld.every == 0))) {
-        const mipx::LpdiveOut dl((size_t)ld.cap);
-        char *dout = ld.d_out[bi];
-        HIP_TRY(ctx, hipEventRecord(ld.e0[bi], st));
+        const auto dl = mipx::LpdiveOut((size_t)ld.cap).view(ld.ring.d_out[bi]);
+        if (int e = ld.ring.begin(ctx, bi, st)) return e;
         const int drc = lpdive_launch(t->prob, st, P, S.d_x, t->pool_l, t->pool_u, S.d_slot, nullptr, S.d.status, S.d_vout,
                                       t->d_int_idx, t->n_int, ld.d_locks, tree_cutoff(t), ld.max_rounds, ld.rule, false, ld.d_ws,
-                                      ld.d_x[bi], (double *)(dout + dl.obj), (int32_t *)(dout + dl.status),
-                                      (int32_t *)(dout + dl.rounds), (int32_t *)(dout + dl.fixings),
-                                      (int32_t *)(dout + dl.flips), (int32_t *)(dout + dl.pivots));
+                                      ld.ring.d_x[bi], dl.obj, dl.status, dl.rounds, dl.fixings, dl.flips, dl.pivots);
         if (drc) return drc;
-        HIP_TRY(ctx, hipEventRecord(ld.e1[bi], st));
+        if (int e = ld.ring.end(ctx, bi, st)) return e;
         S.lpdive_n = P;
     }
     return MIPX_OK;
+}
+
+// The local search's counters over one block of `count` points: its own, or the one it fills inside the block of the
+// dive, the weighted repair or the cube search.
+void ls_count(LsState &ls, const int32_t *status, const int32_t *moves, int count) {
+    for (int k = 0; k < count; k++) {
+        if (status[k] == MIPX_LS_SKIPPED) continue;
+        ls.run++;
+        ls.singles += moves[2 * k];
+        ls.pairs += moves[2 * k + 1];
+        if (moves[2 * k] + moves[2 * k + 1] > 0) ls.improved++;
+        if (status[k] == MIPX_LS_CAPPED) ls.capped++;
+    }
 }
 
 // ... and what it found, before the step's nodes are evaluated: the best feasible point (ties: the lowest
@@ -1165,11 +1238,9 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
     const int bi = (int)(&S - t->buf), P = S.heur_n, n = t->n;
     S.heur_n = 0;
     const step_layout::HeurOut lay((size_t)hr.cap);
-    int rc = tree_d2h(t, hr.h_out[bi], hr.d_out[bi], lay.bytes());
+    int rc = hr.ring.fetch(t, bi, lay.bytes(), hr.us);
     if (rc) return rc;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, hr.e0[bi], hr.e1[bi]) == hipSuccess) hr.us += 1000.0 * ms;
-    const auto o = lay.view((const char *)hr.h_out[bi]);
+    const auto o = lay.view((const char *)hr.ring.h_out[bi]);
     const double *obj = o.obj; const int32_t *status = o.status, *moves = o.moves;
     // local search: its counters; the objectives above are already the improved ones
     LsState &ls = t->ls;
@@ -1178,18 +1249,10 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
     const int32_t *ls_moves = nullptr;
     if (LP > 0) {
         const step_layout::LsOut llay((size_t)ls.cap);
-        if ((rc = tree_d2h(t, ls.h_out[bi], ls.d_out[bi], llay.bytes()))) return rc;
-        if (hipEventElapsedTime(&ms, ls.e0[bi], ls.e1[bi]) == hipSuccess) ls.us += 1000.0 * ms;
-        const auto lo = llay.view((const int32_t *)ls.h_out[bi]);
+        if ((rc = ls.ring.fetch(t, bi, llay.bytes(), ls.us))) return rc;
+        const auto lo = llay.view((const char *)ls.ring.h_out[bi]);
         ls_moves = lo.moves;
-        for (int k = 0; k < LP; k++) {
-            if (lo.status[k] == MIPX_LS_SKIPPED) continue;
-            ls.run++;
-            ls.singles += lo.moves[2 * k];
-            ls.pairs += lo.moves[2 * k + 1];
-            if (lo.moves[2 * k] + lo.moves[2 * k + 1] > 0) ls.improved++;
-            if (lo.status[k] == MIPX_LS_CAPPED) ls.capped++;
-        }
+        ls_count(ls, lo.status, lo.moves, LP);
     }
     // fix-and-propagate dive: its counters, and which points are its own (their objectives are in its block)
     FpState &fp = t->fp;
@@ -1199,9 +1262,8 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
     const int32_t *fp_ok = nullptr, *fp_ls_moves = nullptr;
     if (FP > 0) {
         const step_layout::FpOut flay((size_t)fp.cap);
-        if ((rc = tree_d2h(t, fp.h_out[bi], fp.d_out[bi], flay.bytes()))) return rc;
-        if (hipEventElapsedTime(&ms, fp.e0[bi], fp.e1[bi]) == hipSuccess) fp.us += 1000.0 * ms;
-        const auto fo = flay.view((const char *)fp.h_out[bi]);
+        if ((rc = fp.ring.fetch(t, bi, flay.bytes(), fp.us))) return rc;
+        const auto fo = flay.view((const char *)fp.ring.h_out[bi]);
         fp_obj = fo.obj;
         fp_ok = fo.lift_status;   // (0: the dive ended feasible and the heuristic's second pass lifted the point)
         for (int k = 0; k < FP; k++) {
@@ -1215,14 +1277,7 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         }
         if (LP > 0) {
             fp_ls_moves = fo.ls_moves;
-            for (int k = 0; k < FP; k++) {
-                if (fo.ls_status[k] == MIPX_LS_SKIPPED) continue;
-                ls.run++;
-                ls.singles += fo.ls_moves[2 * k];
-                ls.pairs += fo.ls_moves[2 * k + 1];
-                if (fo.ls_moves[2 * k] + fo.ls_moves[2 * k + 1] > 0) ls.improved++;
-                if (fo.ls_status[k] == MIPX_LS_CAPPED) ls.capped++;
-            }
+            ls_count(ls, fo.ls_status, fo.ls_moves, FP);
         }
     }
     // weighted row repair: the same in its block (it is never on together with the dive, so fp_* are free for it)
@@ -1231,9 +1286,8 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
     S.wr_n = 0;
     if (WP > 0) {
         const step_layout::WrOut wlay((size_t)wr.cap);
-        if ((rc = tree_d2h(t, wr.h_out[bi], wr.d_out[bi], wlay.bytes()))) return rc;
-        if (hipEventElapsedTime(&ms, wr.e0[bi], wr.e1[bi]) == hipSuccess) wr.us += 1000.0 * ms;
-        const auto wo = wlay.view((const char *)wr.h_out[bi]);
+        if ((rc = wr.ring.fetch(t, bi, wlay.bytes(), wr.us))) return rc;
+        const auto wo = wlay.view((const char *)wr.ring.h_out[bi]);
         fp_obj = wo.obj;
         fp_ok = wo.lift_status;   // (0: the repair ended feasible and the heuristic's second pass lifted the point)
         for (int k = 0; k < WP; k++) {
@@ -1246,14 +1300,7 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         }
         if (LP > 0) {
             fp_ls_moves = wo.ls_moves;
-            for (int k = 0; k < WP; k++) {
-                if (wo.ls_status[k] == MIPX_LS_SKIPPED) continue;
-                ls.run++;
-                ls.singles += wo.ls_moves[2 * k];
-                ls.pairs += wo.ls_moves[2 * k + 1];
-                if (wo.ls_moves[2 * k] + wo.ls_moves[2 * k + 1] > 0) ls.improved++;
-                if (wo.ls_status[k] == MIPX_LS_CAPPED) ls.capped++;
-            }
+            ls_count(ls, wo.ls_status, wo.ls_moves, WP);
         }
     }
     // cube search: its counters, and its points (a family of their own, in their own block)
@@ -1264,9 +1311,8 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
     const int32_t *cu_ok = nullptr, *cu_ls_moves = nullptr;
     if (CP > 0) {
         const step_layout::CubeOut clay((size_t)cu.cap);
-        if ((rc = tree_d2h(t, cu.h_out[bi], cu.d_out[bi], clay.bytes()))) return rc;
-        if (hipEventElapsedTime(&ms, cu.e0[bi], cu.e1[bi]) == hipSuccess) cu.us += 1000.0 * ms;
-        const auto co = clay.view((const char *)cu.h_out[bi]);
+        if ((rc = cu.ring.fetch(t, bi, clay.bytes(), cu.us))) return rc;
+        const auto co = clay.view((const char *)cu.ring.h_out[bi]);
         cu_obj = co.obj;
         cu_ok = co.lift_status;   // (0: the cube held a point and the heuristic's pass lifted it)
         for (int k = 0; k < CP; k++) {
@@ -1279,14 +1325,7 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
         }
         if (LP > 0) {
             cu_ls_moves = co.ls_moves;
-            for (int k = 0; k < CP; k++) {
-                if (co.ls_status[k] == MIPX_LS_SKIPPED) continue;
-                ls.run++;
-                ls.singles += co.ls_moves[2 * k];
-                ls.pairs += co.ls_moves[2 * k + 1];
-                if (co.ls_moves[2 * k] + co.ls_moves[2 * k + 1] > 0) ls.improved++;
-                if (co.ls_status[k] == MIPX_LS_CAPPED) ls.capped++;
-            }
+            ls_count(ls, co.ls_status, co.ls_moves, CP);
         }
     }
     // completion: its counters; a COMPLETED point stands in for its source point below, with the objective of its LP
@@ -1299,9 +1338,8 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
     const int32_t *q_status = nullptr;
     if (QP > 0) {
         const step_layout::CompOut qlay((size_t)cc.cap);
-        if ((rc = tree_d2h(t, cc.h_out[bi], cc.d_out[bi], qlay.bytes()))) return rc;
-        if (hipEventElapsedTime(&ms, cc.e0[bi], cc.e1[bi]) == hipSuccess) cc.us += 1000.0 * ms;
-        const auto qo = qlay.view((const char *)cc.h_out[bi]);
+        if ((rc = cc.ring.fetch(t, bi, qlay.bytes(), cc.us))) return rc;
+        const auto qo = qlay.view((const char *)cc.ring.h_out[bi]);
         q_obj = qo.obj;
         q_status = qo.status;
         for (int k = 0; k < (q_cube ? 2 : 1) * QP; k++) {
@@ -1351,31 +1389,27 @@ int heur_step_collect(mipx_tree *t, StepBuf &S) {
     S.lpdive_n = 0;
     bool best_ld = false;
     if (DP > 0) {
-        const mipx::LpdiveOut dl((size_t)ld.cap);
-        if ((rc = tree_d2h(t, ld.h_out[bi], ld.d_out[bi], dl.bytes()))) return rc;
-        if (hipEventElapsedTime(&ms, ld.e0[bi], ld.e1[bi]) == hipSuccess) ld.us += 1000.0 * ms;
-        const char *ho = ld.h_out[bi];
-        const double *d_obj = (const double *)(ho + dl.obj);
-        const int32_t *d_status = (const int32_t *)(ho + dl.status), *d_fix = (const int32_t *)(ho + dl.fixings),
-                      *d_flip = (const int32_t *)(ho + dl.flips), *d_piv = (const int32_t *)(ho + dl.pivots);
+        const mipx::LpdiveOut dlay((size_t)ld.cap);
+        if ((rc = ld.ring.fetch(t, bi, dlay.bytes(), ld.us))) return rc;
+        const auto dl = dlay.view((const char *)ld.ring.h_out[bi]);
         for (int k = 0; k < DP; k++) {
-            if (d_status[k] == MIPX_LPDIVE_SKIPPED) continue;
+            if (dl.status[k] == MIPX_LPDIVE_SKIPPED) continue;
             ld.tried++;
-            ld.moves += d_fix[k] + d_flip[k];
-            ld.pivots += d_piv[k];
-            if (d_status[k] == MIPX_LPDIVE_INFEASIBLE || d_status[k] == MIPX_LPDIVE_CUTOFF) ld.infeasible++;
-            else if (d_status[k] != MIPX_LPDIVE_FEASIBLE) ld.failed++;
-            if (d_status[k] != MIPX_LPDIVE_FEASIBLE) continue;
+            ld.moves += dl.fixings[k] + dl.flips[k];
+            ld.pivots += dl.pivots[k];
+            if (dl.status[k] == MIPX_LPDIVE_INFEASIBLE || dl.status[k] == MIPX_LPDIVE_CUTOFF) ld.infeasible++;
+            else if (dl.status[k] != MIPX_LPDIVE_FEASIBLE) ld.failed++;
+            if (dl.status[k] != MIPX_LPDIVE_FEASIBLE) continue;
             ld.feasible++;
-            if (best < 0 || d_obj[k] < best_obj) {
-                best = k; best_fp = false; best_cube = false; best_comp = false; best_ld = true; best_obj = d_obj[k];
+            if (best < 0 || dl.obj[k] < best_obj) {
+                best = k; best_fp = false; best_cube = false; best_comp = false; best_ld = true; best_obj = dl.obj[k];
             }
         }
     }
     if (best >= 0 && best_obj < t->primal) {
         t->primal = best_obj;
         // (the block that won: a completed point lies in the completion's, at its source's position)
-        const double *from = best_ld ? ld.d_x[bi] : best_comp ? cc.d_x[bi] + (best_cube ? (size_t)QP * n : 0) : best_cube ? cu.d_x[bi] : hr.d_x[bi];
+        const double *from = best_ld ? ld.ring.d_x[bi] : best_comp ? cc.ring.d_x[bi] + (best_cube ? (size_t)QP * n : 0) : best_cube ? cu.ring.d_x[bi] : hr.ring.d_x[bi];
         if (best_comp) cc.installed++;
         if (best_ld) ld.installed++;
         if ((rc = tree_d2h(t, t->best_x.data(), from + (size_t)best * n, (size_t)n * 8))) return rc;
@@ -1418,13 +1452,13 @@ int prop_step_launch(mipx_tree *t, StepBuf &S) {
     mipx_ctx *ctx = t->ctx;
     hipStream_t st = ctx->stream;
     const int bi = (int)(&S - t->buf), B = S.B;
-    const auto o = step_layout::PropOut((size_t)pg.cap).view(pg.d_out[bi]);
+    const auto o = step_layout::PropOut((size_t)pg.cap).view(pg.ring.d_out[bi]);
     const double cutoff = pg.use_cutoff ? tree_cutoff(t) : std::numeric_limits<double>::infinity();
-    HIP_TRY(ctx, hipEventRecord(pg.e0[bi], st));
+    if (int e = pg.ring.begin(ctx, bi, st)) return e;
     const int rc = prop_launch(t->prob, st, B, S.d_slot, t->pool_l, t->pool_u, t->d_int_idx, t->n_int, cutoff, pg.tol,
                                pg.max_rounds, t->pool_l, t->pool_u, o.status, o.changed, o.rounds, o.capped);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(pg.e1[bi], st));
+    if (int e = pg.ring.end(ctx, bi, st)) return e;
     S.prop_n = B;
     return MIPX_OK;
 }
@@ -1435,11 +1469,9 @@ int prop_step_collect(mipx_tree *t, StepBuf &S, std::vector<uint8_t> &inf) {
     const int bi = (int)(&S - t->buf), B = S.prop_n;
     S.prop_n = 0;
     const step_layout::PropOut lay((size_t)pg.cap);
-    int rc = tree_d2h(t, pg.h_out[bi], pg.d_out[bi], lay.bytes());
+    const int rc = pg.ring.fetch(t, bi, lay.bytes(), pg.us);
     if (rc) return rc;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, pg.e0[bi], pg.e1[bi]) == hipSuccess) pg.us += 1000.0 * ms;
-    const auto o = lay.view((const int32_t *)pg.h_out[bi]);
+    const auto o = lay.view((const char *)pg.ring.h_out[bi]);
     inf.assign((size_t)B, 0);
     for (int k = 0; k < B; k++) {
         pg.nodes++;
@@ -3806,87 +3838,12 @@ void mipx_tree_destroy(mipx_tree *t) {
         if (tr.e0) (void)hipEventDestroy(tr.e0);
         if (tr.e1) (void)hipEventDestroy(tr.e1);
     }
-    {
-        HeurState &hr = t->hr;
-        if (hr.d_lu) (void)hipFree(hr.d_lu);
-        for (int k = 0; k < 3; k++) {
-            if (hr.d_x[k]) (void)hipFree(hr.d_x[k]);
-            if (hr.d_out[k]) (void)hipFree(hr.d_out[k]);
-            if (hr.h_out[k]) (void)hipHostFree(hr.h_out[k]);
-            if (hr.e0[k]) (void)hipEventDestroy(hr.e0[k]);
-            if (hr.e1[k]) (void)hipEventDestroy(hr.e1[k]);
-        }
-    }
-    {
-        PropState &pg = t->pg;
-        for (int k = 0; k < 3; k++) {
-            if (pg.d_out[k]) (void)hipFree(pg.d_out[k]);
-            if (pg.h_out[k]) (void)hipHostFree(pg.h_out[k]);
-            if (pg.e0[k]) (void)hipEventDestroy(pg.e0[k]);
-            if (pg.e1[k]) (void)hipEventDestroy(pg.e1[k]);
-        }
-    }
-    {
-        LsState &ls = t->ls;
-        for (int k = 0; k < 3; k++) {
-            if (ls.d_out[k]) (void)hipFree(ls.d_out[k]);
-            if (ls.h_out[k]) (void)hipHostFree(ls.h_out[k]);
-            if (ls.e0[k]) (void)hipEventDestroy(ls.e0[k]);
-            if (ls.e1[k]) (void)hipEventDestroy(ls.e1[k]);
-        }
-    }
-    {
-        FpState &fp = t->fp;
-        for (int k = 0; k < 3; k++) {
-            if (fp.d_out[k]) (void)hipFree(fp.d_out[k]);
-            if (fp.h_out[k]) (void)hipHostFree(fp.h_out[k]);
-            if (fp.e0[k]) (void)hipEventDestroy(fp.e0[k]);
-            if (fp.e1[k]) (void)hipEventDestroy(fp.e1[k]);
-        }
-    }
-    {
-        WrState &wr = t->wr;
-        for (int k = 0; k < 3; k++) {
-            if (wr.d_out[k]) (void)hipFree(wr.d_out[k]);
-            if (wr.h_out[k]) (void)hipHostFree(wr.h_out[k]);
-            if (wr.e0[k]) (void)hipEventDestroy(wr.e0[k]);
-            if (wr.e1[k]) (void)hipEventDestroy(wr.e1[k]);
-        }
-    }
-    {
-        CubeState &cu = t->cu;
-        if (cu.d_ws) (void)hipFree(cu.d_ws);
-        for (int k = 0; k < 3; k++) {
-            if (cu.d_x[k]) (void)hipFree(cu.d_x[k]);
-            if (cu.d_out[k]) (void)hipFree(cu.d_out[k]);
-            if (cu.h_out[k]) (void)hipHostFree(cu.h_out[k]);
-            if (cu.e0[k]) (void)hipEventDestroy(cu.e0[k]);
-            if (cu.e1[k]) (void)hipEventDestroy(cu.e1[k]);
-        }
-    }
-    {
-        CompState &cc = t->cc;
-        if (cc.d_ws) (void)hipFree(cc.d_ws);
-        for (int k = 0; k < 3; k++) {
-            if (cc.d_x[k]) (void)hipFree(cc.d_x[k]);
-            if (cc.d_out[k]) (void)hipFree(cc.d_out[k]);
-            if (cc.h_out[k]) (void)hipHostFree(cc.h_out[k]);
-            if (cc.e0[k]) (void)hipEventDestroy(cc.e0[k]);
-            if (cc.e1[k]) (void)hipEventDestroy(cc.e1[k]);
-        }
-    }
-    {
-        LpdiveState &ld = t->ld;
-        if (ld.d_ws) (void)hipFree(ld.d_ws);
-        if (ld.d_locks) (void)hipFree(ld.d_locks);
-        for (int k = 0; k < 3; k++) {
-            if (ld.d_x[k]) (void)hipFree(ld.d_x[k]);
-            if (ld.d_out[k]) (void)hipFree(ld.d_out[k]);
-            if (ld.h_out[k]) (void)hipHostFree(ld.h_out[k]);
-            if (ld.e0[k]) (void)hipEventDestroy(ld.e0[k]);
-            if (ld.e1[k]) (void)hipEventDestroy(ld.e1[k]);
-        }
-    }
+    // the step options: their one-off buffers, and the ring behind each one's packed block
+    void *ob[] = {t->hr.d_lu, t->cu.d_ws, t->cc.d_ws, t->ld.d_ws, t->ld.d_locks};
+    for (void *q : ob)
+        if (q) (void)hipFree(q);
+    for (StepRing *r : {&t->hr.ring, &t->pg.ring, &t->ls.ring, &t->fp.ring, &t->wr.ring, &t->cu.ring, &t->cc.ring, &t->ld.ring})
+        r->release();
     {
         RcState &rs = t->rc;
         for (int k = 0; k < 3; k++) {

@@ -1,5 +1,7 @@
 // wrepair_api.hip.h -- the C entries of include/mipx_wrepair.h (included at the end of tree_engine.hip.h, which holds
 // the launch and the per-step halves: wr_launch, and the option's parts of heur_step_launch and heur_step_collect).
+// The buffers behind the option's step block are a StepRing (tree_engine.hip.h): the set entry switches the option off,
+// grows the ring, and switches it on last.  The batch entry's prologue is the shared one of mipx.hip (check_int_idx, ...).
 
 extern "C" {
 
@@ -12,20 +14,12 @@ int mipx_weighted_repair_batch(mipx_problem *p, int batch, const double *x, cons
     if (batch < 0 || n_int < 0 || n_int > p->n || !(tol >= 0.0) || max_steps < 0 || !l || !u || (n_int && !int_idx) ||
         (batch && (!x || !x_out || !obj_out || !status_out || !counts_out)))
         return fail(ctx, MIPX_EINVAL, "mipx_weighted_repair_batch: bad argument");
-    std::vector<uint8_t> seen((size_t)p->n, 0);
-    for (int k = 0; k < n_int; k++) {
-        if (int_idx[k] < 0 || int_idx[k] >= p->n || seen[(size_t)int_idx[k]])
-            return fail(ctx, MIPX_EINVAL, "mipx_weighted_repair_batch: int_idx out of range or repeated");
-        seen[(size_t)int_idx[k]] = 1;
-    }
+    if (int rc = check_int_idx(ctx, "mipx_weighted_repair_batch", int_idx, n_int, p->n)) return rc;
     if (p->m > mipx::kWrMax || p->n > mipx::kWrMax)
         return fail(ctx, MIPX_ETOOBIG, "mipx_weighted_repair_batch: more than 1024 rows or columns");
     const size_t B = (size_t)batch, nn = (size_t)p->n;
-    for (size_t e = 0; e < nn; e++)
-        if (!std::isfinite(l[e]) || u[e] != u[e] || u[e] == -std::numeric_limits<double>::infinity())
-            return fail(ctx, MIPX_EINVAL, "mipx_weighted_repair_batch: a lower bound that is not finite, or an upper bound that is NaN or -inf");
-    for (size_t e = 0; e < B * nn; e++)
-        if (!std::isfinite(x[e])) return fail(ctx, MIPX_EINVAL, "mipx_weighted_repair_batch: a point that is not finite");
+    if (int rc = check_bounds(ctx, "mipx_weighted_repair_batch", nullptr, l, u, nn)) return rc;
+    if (int rc = check_points(ctx, "mipx_weighted_repair_batch", x, B * nn)) return rc;
     if (batch == 0) return MIPX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Staging S(ctx, "mipx_weighted_repair_batch");
@@ -62,17 +56,10 @@ int mipx_tree_set_weighted_repair(mipx_tree *t, int max_steps) {
         return fail(ctx, MIPX_EINVAL, "mipx_tree_set_weighted_repair: not with the fix-and-propagate dive (mipx_tree_set_fix_propagate(t, 1, 0) first)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (t->hr.cap > wr.cap) {   // (the heuristic's step buffers grew or are new: nothing is in flight before the first step)
-        const size_t out_bytes = step_layout::WrOut((size_t)t->hr.cap).bytes();
-        for (int k = 0; k < 3; k++) {
-            if (wr.d_out[k]) (void)hipFree(wr.d_out[k]);
-            if (wr.h_out[k]) (void)hipHostFree(wr.h_out[k]);
-            wr.d_out[k] = nullptr; wr.h_out[k] = nullptr;
-            int rc = dmalloc(ctx, &wr.d_out[k], out_bytes);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipHostMalloc((void **)&wr.h_out[k], out_bytes));
-            if (!wr.e0[k]) HIP_TRY(ctx, hipEventCreate(&wr.e0[k]));
-            if (!wr.e1[k]) HIP_TRY(ctx, hipEventCreate(&wr.e1[k]));
-        }
+        wr.on = false;   // (until every block is there: a failure below leaves the option off and nothing to launch on)
+        wr.cap = 0;
+        const int rc = wr.ring.grow(ctx, step_layout::WrOut((size_t)t->hr.cap).bytes(), 0);
+        if (rc) return rc;
         wr.cap = t->hr.cap;   // (laid out for wr.cap points: step_layout::WrOut)
     }
     wr.max_steps = max_steps;

@@ -14,7 +14,7 @@ from simple_mip_solver_amd.generators import random_dense_milp_arrays
 from simple_mip_solver_amd.lp import CyLPArray
 from tests.support import cglp_reference as highs
 from tests.support import cglp_screen_reference as ref
-from tests.support.abi_check import agrees, prototypes
+from tests.support.abi_check import agrees, library_prerequisites, prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ['mipx_tree_support_open_ex', 'mipx_tree_support_eval_ex', 'mipx_support_screen_batch']
@@ -210,7 +210,7 @@ def test_mipx_h_includes_the_header_and_the_constants_match():
     assert 'mipx_cglp_screen.h' in open(os.path.join(ROOT, 'include', 'mipx_cglp.h')).read()
     kernels = open(os.path.join(ROOT, 'simple_mip_solver_amd', 'csrc', 'cglp_screen_kernels.hip.h')).read()
     assert int(re.search(r'kScrMax = (\d+)', kernels).group(1)) == 1024 and 'above 1024' in head
-    assert 'mipx_cglp_screen.h' in open(os.path.join(ROOT, 'simple_mip_solver_amd', 'csrc', 'Makefile')).read()
+    assert os.path.join(ROOT, 'include', 'mipx_cglp_screen.h') in library_prerequisites()   # (a change of the header rebuilds the library)
     assert len(_ffi.CGLP_EXTRA_KEYS) == 6 and 'extra (null, or 6 doubles)' in head
 
 

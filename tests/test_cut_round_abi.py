@@ -10,7 +10,7 @@ import pytest
 
 from simple_mip_solver_amd import _ffi
 from tests.support import cut_round_reference as ref
-from tests.support.abi_check import agrees, prototypes
+from tests.support.abi_check import agrees, library_prerequisites, prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ['mipx_cut_round_begin_batch', 'mipx_cut_round_generate_batch']
@@ -83,7 +83,7 @@ def test_the_round_kernels_are_launched_from_one_place():
     assert text.count('enqueue_cut_begin(') == 3 and text.count('enqueue_cut_generate(') == 2          # the definition and the engine's calls
     assert api.count('enqueue_cut_begin(') == 1 and api.count('enqueue_cut_generate(') == 1 and 'hipLaunchKernelGGL' not in api
     assert text.rstrip().endswith('#include "cutround_api.hip.h"')
-    assert 'mipx_cutround.h' in open(os.path.join(csrc, 'Makefile')).read()
+    assert os.path.join(ROOT, 'include', 'mipx_cutround.h') in library_prerequisites()   # (a change of the header rebuilds the library)
 
 
 # ---- hand-worked rounds ------------------------------------------------------------------------------------------
