@@ -612,5 +612,6 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_mir.h"     /* mixed-integer rounding cuts: batched separation of base rows on the GPU */
 #include "mipx_cover.h"   /* lifted knapsack cover cuts: batched separation from the rows on the GPU */
 #include "mipx_dualfn_batch.h" /* test scaffolding: the kernels of the dual function on a caller's records */
+#include "mipx_noderows.h"     /* test scaffolding: the kernels that move node rows on a caller's pools */
 
 #endif /* MIPX_H */

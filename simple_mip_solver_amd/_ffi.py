@@ -454,6 +454,24 @@ _DUALFN_BATCH_SIGNATURES = {
     'mipx_dualfn_eval_batch': (_i, [_vp] + [_i] * 4 + [_vp] * 6 + [_i, _vp, _i, _i] + [_vp] * 3),
 }
 DUALFN_BATCH_SYMBOLS = list(_DUALFN_BATCH_SIGNATURES)
+# ... and those of include/mipx_noderows.h (test scaffolding: the kernels that move node rows on a caller's pools),
+# which mipx.h includes (tests/test_node_rows_abi.py checks them against that header)
+_NODEROWS_SIGNATURES = {
+    'mipx_noderows_children': (_i, [_vp] + [_i] * 6 + [_vp] * 2 + [_i] + [_vp] * 8 + [_i] + [_vp] * 5),
+    'mipx_noderows_pack': (_i, [_vp, _i, _i, _i, _vp, _i] + [_vp] * 4),
+    'mipx_noderows_unpack': (_i, [_vp, _i, _i, _i, _vp, _vp, _i] + [_vp] * 3),
+    'mipx_noderows_gather_plain': (_i, [_vp] + [_i] * 4 + [_vp, _i] + [_vp] * 6),
+    'mipx_noderows_lineage_bounds': (_i, [_vp, _i, _i, _i64] + [_vp] * 3 + [_i] + [_vp] * 7),
+    'mipx_noderows_lineage_seed': (_i, [_vp, _i, _i, _i64] + [_vp] * 3 + [_i, _vp, _vp, _i64] + [_vp] * 6),
+    'mipx_noderows_cut_lists': (_i, [_vp, _i, _i, _vp, _i] + [_vp] * 3),
+    'mipx_noderows_cut_gather': (_i, [_vp, _i, _i, _vp, _i64] + [_vp] * 4),
+    'mipx_noderows_cut_scatter': (_i, [_vp, _i, _i, _i64, _vp, _vp, _i64, _vp, _vp]),
+    'mipx_noderows_cut_unpack_lists': (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _i] + [_vp] * 3),
+    'mipx_noderows_spill_pack': (_i, [_vp] + [_i] * 4 + [_vp, _vp, _i] + [_vp] * 9 + [_i64, _vp]),
+    'mipx_noderows_spill_unpack': (_i, [_vp] + [_i] * 4 + [_vp] * 5 + [_i] + [_vp] * 5),
+    'mipx_noderows_spill_gather_rows': (_i, [_vp, _i, _i, _i, _vp, _i] + [_vp] * 6),
+}
+NODEROWS_SYMBOLS = list(_NODEROWS_SIGNATURES)
 MIR_STATUS = {0: 'cut', 1: 'no_trial', 2: 'shallow', 3: 'dynamism', 4: 'skipped'}   # MIPX_MIR_* of the header
 COVER_STATUS = {0: 'cut', 1: 'no_cover', 2: 'shallow', 4: 'skipped'}   # MIPX_COVER_* of include/mipx_cover.h
 # the defaults of the separation: divisor candidates per row (at most MIR_MAX_DIVISORS), the window of f0, the largest
@@ -490,6 +508,7 @@ def lib():
                                       list(_LPDIVE_SIGNATURES.items()) + list(_FINISH_SIGNATURES.items()) +
                                       list(_CUTROUND_SIGNATURES.items()) + list(_CGLP_SCREEN_SIGNATURES.items()) +
                                       list(_MIR_SIGNATURES.items()) + list(_DUALFN_BATCH_SIGNATURES.items()) +
+                                      list(_NODEROWS_SIGNATURES.items()) +
                                       list(_COVER_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
@@ -981,6 +1000,148 @@ def dualfn_eval_batch(ctx, ev, k_tile=0, fill=0x5a):
                                       _ptr(out['V_gemm']), _ptr(out['V_max']), _ptr(out['out']))
     ctx.check(rc, 'mipx_dualfn_eval_batch')
     return out
+
+
+# ---- test scaffolding of include/mipx_noderows.h: the kernels that move node rows, on a caller's pools ------------------
+# An array that is in and out must be a C-contiguous array of its C type: it is written in place, whole (the callers
+# hand in sentinel-filled copies).  Inputs are converted.  A refused call raises MipxError and writes nothing.
+def _io(a, dtype):
+    assert a is None or (isinstance(a, np.ndarray) and a.dtype == np.dtype(dtype) and a.flags['C_CONTIGUOUS'] and a.flags['WRITEABLE'])
+    return _ptr(a)
+
+
+def noderows_children(ctx, n, m, src_l, src_u, x, vstat, parent_slot, parent_pos, var, child_slot, dst_l, dst_u, dst_v,
+                      mstride=0, kc=0, src_ncut=None, src_ids=None, dst_ncut=None, dst_ids=None):
+    """make_children (mipx_noderows_children): dst_* are written in place."""
+    src_l, src_u, x = _arr(src_l, np.float64, (-1, n)), _arr(src_u, np.float64, (-1, n)), _arr(x, np.float64, (-1, n))
+    vstat = _arr(vstat, np.int8, (len(x), -1))
+    ps, pp, va, cs = (_arr(a, np.int32) for a in (parent_slot, parent_pos, var, child_slot))
+    src_ncut, src_ids = _arr(src_ncut, np.int32), _arr(src_ids, np.int32)
+    rc = lib().mipx_noderows_children(ctx._h, n, m, mstride, kc, len(ps), len(src_l), _ptr(src_l), _ptr(src_u), len(x), _ptr(x),
+                                      _ptr(vstat), _ptr(src_ncut), _ptr(src_ids), _ptr(ps), _ptr(pp), _ptr(va), _ptr(cs),
+                                      len(dst_l), _io(dst_l, np.float64), _io(dst_u, np.float64), _io(dst_v, np.int8),
+                                      _io(dst_ncut, np.int32), _io(dst_ids, np.int32))
+    ctx.check(rc, 'mipx_noderows_children')
+
+
+def noderows_pack(ctx, n, nvs, slot, pool_l, pool_u, pool_v, msg):
+    """pack_nodes (mipx_noderows_pack): msg (uint8, count x rowbytes) is written in place."""
+    slot = _arr(slot, np.int32)
+    pool_l, pool_u, pool_v = _arr(pool_l, np.float64, (-1, n)), _arr(pool_u, np.float64, (-1, n)), _arr(pool_v, np.int8, (-1, nvs))
+    rc = lib().mipx_noderows_pack(ctx._h, n, nvs, len(slot), _ptr(slot), len(pool_l), _ptr(pool_l), _ptr(pool_u), _ptr(pool_v),
+                                  _io(msg, np.uint8))
+    ctx.check(rc, 'mipx_noderows_pack')
+
+
+def noderows_unpack(ctx, n, nvs, slot, msg, pool_l, pool_u, pool_v):
+    """unpack_nodes (mipx_noderows_unpack): the pool is written in place."""
+    slot, msg = _arr(slot, np.int32), _arr(msg, np.uint8)
+    rc = lib().mipx_noderows_unpack(ctx._h, n, nvs, len(slot), _ptr(slot), _ptr(msg), len(pool_l), _io(pool_l, np.float64),
+                                    _io(pool_u, np.float64), _io(pool_v, np.int8))
+    ctx.check(rc, 'mipx_noderows_unpack')
+
+
+def noderows_gather_plain(ctx, n, m, nvs_pool, slot, pool_l, pool_u, pool_v, l, u, v):
+    """gather_plain_nodes (mipx_noderows_gather_plain): l, u, v are written in place."""
+    slot = _arr(slot, np.int32)
+    pool_l, pool_u = _arr(pool_l, np.float64, (-1, n)), _arr(pool_u, np.float64, (-1, n))
+    pool_v = _arr(pool_v, np.int8, (len(pool_l), -1))
+    rc = lib().mipx_noderows_gather_plain(ctx._h, n, m, nvs_pool, len(slot), _ptr(slot), len(pool_l), _ptr(pool_l), _ptr(pool_u),
+                                          _ptr(pool_v), _io(l, np.float64), _io(u, np.float64), _io(v, np.int8))
+    ctx.check(rc, 'mipx_noderows_gather_plain')
+
+
+def _lineage_in(n, nv, parent, vd, val, ids, root_l, root_u, root_v):
+    parent, vd, val = _arr(parent, np.int32), _arr(vd, np.int32), _arr(val, np.float64)
+    assert len(parent) == len(vd) == len(val)
+    return parent, vd, val, _arr(ids, np.int64), _arr(root_l, np.float64, n), _arr(root_u, np.float64, n), _arr(root_v, np.int8, nv)
+
+
+def noderows_lineage_bounds(ctx, n, nv, parent, vd, val, ids, root_l, root_u, root_v, out_l, out_u, out_v):
+    """treerec_bounds on a mirror (mipx_noderows_lineage_bounds): out_* are written in place."""
+    parent, vd, val, ids, rl, ru, rv = _lineage_in(n, nv, parent, vd, val, ids, root_l, root_u, root_v)
+    rc = lib().mipx_noderows_lineage_bounds(ctx._h, n, nv, len(parent), _ptr(parent), _ptr(vd), _ptr(val), len(ids), _ptr(ids),
+                                            _ptr(rl), _ptr(ru), _ptr(rv), _io(out_l, np.float64), _io(out_u, np.float64),
+                                            _io(out_v, np.int8))
+    ctx.check(rc, 'mipx_noderows_lineage_bounds')
+
+
+def noderows_lineage_seed(ctx, n, nv, parent, vd, val, ids, slots, root_l, root_u, root_v, pool_l, pool_u, pool_v):
+    """restart_seed on a mirror (mipx_noderows_lineage_seed): the pool (capacity = its rows) is written in place."""
+    parent, vd, val, ids, rl, ru, rv = _lineage_in(n, nv, parent, vd, val, ids, root_l, root_u, root_v)
+    slots = _arr(slots, np.int32)
+    assert len(slots) == len(ids)
+    rc = lib().mipx_noderows_lineage_seed(ctx._h, n, nv, len(parent), _ptr(parent), _ptr(vd), _ptr(val), len(ids), _ptr(ids),
+                                          _ptr(slots), len(pool_l), _ptr(rl), _ptr(ru), _ptr(rv), _io(pool_l, np.float64),
+                                          _io(pool_u, np.float64), _io(pool_v, np.int8))
+    ctx.check(rc, 'mipx_noderows_lineage_seed')
+
+
+def noderows_cut_lists(ctx, kc, slot, pool_ncut, pool_ids, lists):
+    """cutmig_lists (mipx_noderows_cut_lists): lists (count x (1 + kc) int32) is written in place."""
+    slot, pool_ncut, pool_ids = _arr(slot, np.int32), _arr(pool_ncut, np.int32), _arr(pool_ids, np.int32, (-1, kc))
+    rc = lib().mipx_noderows_cut_lists(ctx._h, kc, len(slot), _ptr(slot), len(pool_ncut), _ptr(pool_ncut), _ptr(pool_ids),
+                                       _io(lists, np.int32))
+    ctx.check(rc, 'mipx_noderows_cut_lists')
+
+
+def noderows_cut_gather(ctx, n, src, store_pi, store_pi0, tab_pi, tab_pi0):
+    """cutmig_gather (mipx_noderows_cut_gather): the table is written in place."""
+    src, store_pi, store_pi0 = _arr(src, np.int32), _arr(store_pi, np.float64, (-1, n)), _arr(store_pi0, np.float64)
+    rc = lib().mipx_noderows_cut_gather(ctx._h, n, len(src), _ptr(src), len(store_pi0), _ptr(store_pi), _ptr(store_pi0),
+                                        _io(tab_pi, np.float64), _io(tab_pi0, np.float64))
+    ctx.check(rc, 'mipx_noderows_cut_gather')
+
+
+def noderows_cut_scatter(ctx, n, base, tab_pi, tab_pi0, store_pi, store_pi0):
+    """cutmig_scatter (mipx_noderows_cut_scatter): the store is written in place."""
+    tab_pi, tab_pi0 = _arr(tab_pi, np.float64, (-1, n)), _arr(tab_pi0, np.float64)
+    rc = lib().mipx_noderows_cut_scatter(ctx._h, n, len(tab_pi0), int(base), _ptr(tab_pi), _ptr(tab_pi0), len(store_pi0),
+                                         _io(store_pi, np.float64), _io(store_pi0, np.float64))
+    ctx.check(rc, 'mipx_noderows_cut_scatter')
+
+
+def noderows_cut_unpack_lists(ctx, kc, slot, lists, base, ctab, pool_ncut, pool_ids):
+    """cutmig_unpack_lists (mipx_noderows_cut_unpack_lists): the pool's lists are written in place; returns bad."""
+    slot, lists = _arr(slot, np.int32), _arr(lists, np.int32, (-1, 1 + kc))
+    bad = np.full(1, -1, np.int32)
+    rc = lib().mipx_noderows_cut_unpack_lists(ctx._h, kc, len(slot), _ptr(slot), _ptr(lists), int(base), int(ctab), len(pool_ncut),
+                                              _io(pool_ncut, np.int32), _io(pool_ids, np.int32), _ptr(bad))
+    ctx.check(rc, 'mipx_noderows_cut_unpack_lists')
+    return int(bad[0])
+
+
+def noderows_spill_pack(ctx, n, nv, kc, count, root_l, root_u, l, u, v, ncut, ids, slot, node_id, out_offsets, out_bytes):
+    """spill_count, spill_scan, spill_pack (mipx_noderows_spill_pack): out_offsets (count + 1 int64) and out_bytes
+    (uint8, its size is the capacity) are written in place; returns the records' total bytes."""
+    rl, ru = _arr(root_l, np.float64, n), _arr(root_u, np.float64, n)
+    l, u, v = _arr(l, np.float64, (-1, n)), _arr(u, np.float64, (-1, n)), _arr(v, np.int8, (-1, nv))
+    ncut, ids, slot, node_id = _arr(ncut, np.int32), _arr(ids, np.int32), _arr(slot, np.int32), _arr(node_id, np.int64)
+    used = np.zeros(1, np.int64)
+    rc = lib().mipx_noderows_spill_pack(ctx._h, n, nv, kc, count, _ptr(rl), _ptr(ru), len(l), _ptr(l), _ptr(u), _ptr(v), _ptr(ncut),
+                                        _ptr(ids), _ptr(slot), _ptr(node_id), _io(out_offsets, np.int64), _io(out_bytes, np.uint8),
+                                        out_bytes.size, _ptr(used))
+    ctx.check(rc, 'mipx_noderows_spill_pack')
+    return int(used[0])
+
+
+def noderows_spill_unpack(ctx, n, nv, kc, root_l, root_u, offsets, records, slot, l, u, v, ncut=None, ids=None):
+    """spill_unpack (mipx_noderows_spill_unpack): the pool's arrays are written in place."""
+    rl, ru = _arr(root_l, np.float64, n), _arr(root_u, np.float64, n)
+    offsets, records, slot = _arr(offsets, np.int64), _arr(records, np.uint8), _arr(slot, np.int32)
+    rc = lib().mipx_noderows_spill_unpack(ctx._h, n, nv, kc, len(offsets) - 1, _ptr(rl), _ptr(ru), _ptr(offsets), _ptr(records),
+                                          _ptr(slot), len(l), _io(l, np.float64), _io(u, np.float64), _io(v, np.int8),
+                                          _io(ncut, np.int32), _io(ids, np.int32))
+    ctx.check(rc, 'mipx_noderows_spill_unpack')
+
+
+def noderows_spill_gather_rows(ctx, n, nv, slot, src_l, src_u, src_v, l, u, v):
+    """spill_gather_rows (mipx_noderows_spill_gather_rows): l, u, v are written in place."""
+    slot = _arr(slot, np.int32)
+    src_l, src_u, src_v = _arr(src_l, np.float64, (-1, n)), _arr(src_u, np.float64, (-1, n)), _arr(src_v, np.int8, (-1, nv))
+    rc = lib().mipx_noderows_spill_gather_rows(ctx._h, n, nv, len(slot), _ptr(slot), len(src_l), _ptr(src_l), _ptr(src_u),
+                                               _ptr(src_v), _io(l, np.float64), _io(u, np.float64), _io(v, np.int8))
+    ctx.check(rc, 'mipx_noderows_spill_gather_rows')
 
 
 def solve_multi(ctx, A, b, c, l, u, max_iter=0):

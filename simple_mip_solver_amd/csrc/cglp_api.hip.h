@@ -70,10 +70,10 @@ int sup_bounds(mipx_support *s) {
     for (int64_t k0 = 0; k0 < s->T; k0 += kTrChunk) {
         const int cnt = (int)std::min(kTrChunk, s->T - k0);
         mipx::TrBoundsArgs a;
-        a.n = s->n; a.nv = (int)nv; a.count = cnt; a.nodes_count = tr.d_count; a.nodes = tr.d_nodes; a.ids = s->d_ids + k0;
+        a.n = s->n; a.nv = (int)nv; a.nodes_count = tr.d_count; a.nodes = tr.d_nodes; a.ids = s->d_ids + k0;
         a.root_l = tr.d_root; a.root_u = tr.d_root + n; a.root_v = tr.have_root ? tr.d_root_v : nullptr;
         a.out_l = s->d_l + (size_t)k0 * n; a.out_u = s->d_u + (size_t)k0 * n; a.out_v = s->d_v[s->cur] + (size_t)k0 * nv;
-        hipLaunchKernelGGL(mipx::treerec_bounds, dim3((unsigned)cnt), dim3(mipx::kTrNT), n, st, a);
+        enqueue_treerec_bounds(a, cnt, st);
         HIP_TRY(ctx, hipGetLastError());
         tr.materialised += cnt;
     }

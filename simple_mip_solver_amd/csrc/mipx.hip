@@ -399,6 +399,29 @@ int timed_launch_finish(Staging &S, int rc, Launch launch) {
 #include "cut_kernels.hip.h"
 #include "comm.hip.h"
 #include "spill_kernels.hip.h"
+
+namespace {
+// the records of a spill message against their own headers, before any kernel reads them
+int spill_check_records(mipx_ctx *ctx, const char *who, int n, int nv, int kcut, size_t B, const int64_t *offsets,
+                        const char *rec) {
+    if (offsets[0] != 0) return refuse(ctx, who, "offsets[0] must be 0");
+    for (size_t k = 0; k < B; k++) {
+        const int64_t o = offsets[k], len = offsets[k + 1] - o;
+        if (o % 8 != 0 || len < 16) return refuse(ctx, who, "bad offsets");
+        int32_t hd[2];
+        std::memcpy(hd, rec + o + 8, 8);
+        if (hd[0] < 0 || hd[0] > n || hd[1] < 0 || (kcut > 0 ? hd[1] > kcut : hd[1] != 0) ||
+            mipx::spill_record_bytes(hd[0], hd[1], nv, kcut) != len)
+            return refuse(ctx, who, "a record disagrees with its header");
+        const int32_t *col = (const int32_t *)(rec + o + 16);
+        for (int32_t q = 0; q < hd[0]; q++)
+            if (col[q] < 0 || col[q] >= n || (q > 0 && col[q] <= col[q - 1]))
+                return refuse(ctx, who, "diff columns must ascend within [0, n)");
+    }
+    return MIPX_OK;
+}
+}  // namespace
+
 #include "tree_engine.hip.h"
 #include "mir_kernels.hip.h"
 #include "mir_api.hip.h"
@@ -1031,15 +1054,15 @@ int mipx_node_pack_batch(mipx_ctx *ctx, int n, int nv, int count, const double *
     int rc = S.alloc();
     if (rc == MIPX_OK) rc = S.upload();
     mipx::SpillArgs a;
-    a.n = n; a.nv = nv; a.kc = kcut; a.count = count;
+    a.n = n; a.nv = nv; a.kc = kcut;
     a.root_l = S.at<const double>(o_rl); a.root_u = S.at<const double>(o_ru);
     a.l = S.at<double>(o_l); a.u = S.at<double>(o_u); a.v = S.at<int8_t>(o_v);
     a.ncut = S.at<int32_t>(o_nc); a.ids = S.at<int32_t>(o_id); a.off = S.at<int64_t>(o_off); a.rec = S.at<char>(o_rec);
     hipStream_t st = ctx->stream;
     if (rc == MIPX_OK && count > 0) {
-        hipLaunchKernelGGL(mipx::spill_count, dim3((count + 3) / 4), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(mipx::spill_scan, dim3(1), dim3(1024), 0, st, a);
-        hipLaunchKernelGGL(mipx::spill_pack, dim3((count + 3) / 4), dim3(256), 0, st, a);
+        enqueue_spill_count(a, count, st);
+        enqueue_spill_scan(a, count, st);
+        enqueue_spill_pack(a, count, st);
         if (hipError_t e = hipGetLastError()) rc = S.err("launch", e);
     }
     if (count == 0 && rc == MIPX_OK && hipMemsetAsync(a.off, 0, 8, st) != hipSuccess) rc = S.err("memset", hipGetLastError());
@@ -1068,21 +1091,7 @@ int mipx_node_unpack_batch(mipx_ctx *ctx, int n, int nv, int count, const double
     if (count == 0) return MIPX_OK;
     const size_t B = (size_t)count, kc = (size_t)kcut;
     // the records are checked against their own headers before any kernel reads them
-    const char *rec = (const char *)in_bytes;
-    if (offsets[0] != 0) return fail(ctx, MIPX_EINVAL, "mipx_node_unpack_batch: offsets[0] must be 0");
-    for (size_t k = 0; k < B; k++) {
-        const int64_t o = offsets[k], len = offsets[k + 1] - o;
-        if (o % 8 != 0 || len < 16) return fail(ctx, MIPX_EINVAL, "mipx_node_unpack_batch: bad offsets");
-        int32_t hd[2];
-        std::memcpy(hd, rec + o + 8, 8);
-        if (hd[0] < 0 || hd[0] > n || hd[1] < 0 || (kcut > 0 ? hd[1] > kcut : hd[1] != 0) ||
-            mipx::spill_record_bytes(hd[0], hd[1], nv, kcut) != len)
-            return fail(ctx, MIPX_EINVAL, "mipx_node_unpack_batch: a record disagrees with its header");
-        const int32_t *col = (const int32_t *)(rec + o + 16);
-        for (int32_t q = 0; q < hd[0]; q++)
-            if (col[q] < 0 || col[q] >= n || (q > 0 && col[q] <= col[q - 1]))
-                return fail(ctx, MIPX_EINVAL, "mipx_node_unpack_batch: diff columns must ascend within [0, n)");
-    }
+    if (int rc = spill_check_records(ctx, "mipx_node_unpack_batch", n, nv, kcut, B, offsets, (const char *)in_bytes)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Staging S(ctx, "mipx_node_unpack_batch");
     const size_t o_rl = S.in(root_l, (size_t)n * 8), o_ru = S.in(root_u, (size_t)n * 8), o_off = S.in(offsets, (B + 1) * 8),
@@ -1093,12 +1102,12 @@ int mipx_node_unpack_batch(mipx_ctx *ctx, int n, int nv, int count, const double
     int rc = S.alloc();
     if (rc == MIPX_OK) rc = S.upload();
     mipx::SpillArgs a;
-    a.n = n; a.nv = nv; a.kc = kcut; a.count = count;
+    a.n = n; a.nv = nv; a.kc = kcut;
     a.root_l = S.at<const double>(o_rl); a.root_u = S.at<const double>(o_ru);
     a.l = S.at<double>(o_l); a.u = S.at<double>(o_u); a.v = S.at<int8_t>(o_v);
     a.ncut = S.at<int32_t>(o_nc); a.ids = S.at<int32_t>(o_id); a.off = S.at<int64_t>(o_off); a.rec = S.at<char>(o_rec);
     if (rc == MIPX_OK) {
-        hipLaunchKernelGGL(mipx::spill_unpack, dim3((count + 3) / 4), dim3(256), 0, ctx->stream, a);
+        enqueue_spill_unpack(a, count, ctx->stream);
         if (hipError_t e = hipGetLastError()) rc = S.err("launch", e);
     }
     return S.finish(rc);

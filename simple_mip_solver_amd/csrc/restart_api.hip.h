@@ -23,13 +23,13 @@ int restart_seed_rows(mipx_tree *t, const std::vector<int32_t> &slots) {
         hipError_t e = hipMemcpyAsync(d_ids, rs.seeds.data() + k0, (size_t)cnt * 8, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_slots, slots.data() + k0, (size_t)cnt * 4, hipMemcpyHostToDevice, st);
         mipx::RestartSeedArgs a;
-        a.n = t->n; a.nv = t->n + t->mrows; a.count = cnt; a.nodes_count = tr.d_count; a.capacity = t->capacity;
+        a.n = t->n; a.nv = t->n + t->mrows; a.nodes_count = tr.d_count; a.capacity = t->capacity;
         a.nodes = tr.d_nodes; a.ids = d_ids; a.slots = d_slots;
         a.root_l = tr.d_root; a.root_u = tr.d_root + t->n; a.root_v = tr.have_root ? tr.d_root_v : nullptr;
         a.pool_l = t->pool_l; a.pool_u = t->pool_u; a.pool_v = t->pool_v;
         if (e == hipSuccess) e = hipEventRecord(tr.e0, st);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(mipx::restart_seed, dim3((unsigned)cnt), dim3(mipx::kTrNT), (size_t)t->n, st, a);
+            enqueue_restart_seed(a, cnt, st);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipEventRecord(tr.e1, st);

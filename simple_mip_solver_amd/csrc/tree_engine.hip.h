@@ -36,6 +36,78 @@
 #include "cglp_screen_kernels.hip.h"
 #include "step_layout.h"
 
+// The one launch site of each kernel that moves node rows (make_children, the message kernels, the lineage kernels,
+// the cut-migration kernels, the spill kernels): grid, block and LDS rule live here.  `count` -- records, rows or
+// (parent, variable) pairs -- is set into the args here and nowhere else: the callers leave a.count alone.  The engine and the entries of include/mipx_noderows.h
+// (noderows_api.hip.h) both launch through these, so the tests of those entries run the engine's launches.
+namespace {
+inline unsigned rows_grid4(int count) { return (unsigned)(((int64_t)count + 3) / 4); }   // one wave64 per record, four per block
+
+void enqueue_make_children(mipx::ChildArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::make_children, dim3(2 * (unsigned)count), dim3(256), 0, st, a);
+}
+void enqueue_pack_nodes(mipx::PackArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::pack_nodes, dim3((unsigned)count), dim3(256), 0, st, a);
+}
+void enqueue_unpack_nodes(mipx::PackArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::unpack_nodes, dim3((unsigned)count), dim3(256), 0, st, a);
+}
+void enqueue_gather_plain_nodes(mipx::PlainGatherArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::gather_plain_nodes, dim3((unsigned)count), dim3(256), 0, st, a);
+}
+// (the lineage kernels keep one byte per column in LDS: n bytes)
+void enqueue_treerec_bounds(mipx::TrBoundsArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::treerec_bounds, dim3((unsigned)count), dim3(mipx::kTrNT), (size_t)a.n, st, a);
+}
+void enqueue_restart_seed(mipx::RestartSeedArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::restart_seed, dim3((unsigned)count), dim3(mipx::kTrNT), (size_t)a.n, st, a);
+}
+void enqueue_cutmig_lists(mipx::CutMigArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::cutmig_lists, dim3(rows_grid4(count)), dim3(256), 0, st, a);
+}
+void enqueue_cutmig_gather(mipx::CutMigArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::cutmig_gather, dim3(rows_grid4(count)), dim3(256), 0, st, a);
+}
+void enqueue_cutmig_scatter(mipx::CutMigArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::cutmig_scatter, dim3(rows_grid4(count)), dim3(256), 0, st, a);
+}
+void enqueue_cutmig_unpack_lists(mipx::CutMigArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::cutmig_unpack_lists, dim3(rows_grid4(count)), dim3(256), 0, st, a);
+}
+// sizes (spill_count), then their exclusive offsets in place (spill_scan): a.off holds count + 1 entries
+void enqueue_spill_count(mipx::SpillArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::spill_count, dim3(rows_grid4(count)), dim3(256), 0, st, a);
+}
+void enqueue_spill_scan(mipx::SpillArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::spill_scan, dim3(1), dim3(1024), 0, st, a);
+}
+void enqueue_spill_pack(mipx::SpillArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::spill_pack, dim3(rows_grid4(count)), dim3(256), 0, st, a);
+}
+void enqueue_spill_unpack(mipx::SpillArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::spill_unpack, dim3(rows_grid4(count)), dim3(256), 0, st, a);
+}
+void enqueue_spill_gather_rows(mipx::SpillArgs a, int count, hipStream_t st, const double *src_l, const double *src_u,
+                               const int8_t *src_v) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::spill_gather_rows, dim3((unsigned)count), dim3(256), 0, st, a, src_l, src_u, src_v);
+}
+}  // namespace
+
 struct NodeRec {
     double key;          // queue key: dual bound (best first) or -depth (depth first)
     double dual_bound;   // bound inherited from the parent (parent's LP objective)
@@ -1919,10 +1991,9 @@ int spill_event(mipx_tree *t, int64_t target) {
     HIP_TRY(ctx, hipMemcpyAsync(h.d_slot, rows.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(h.d_id, ids.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
     mipx::SpillArgs a = spill_args(t);
-    a.count = (int)K; a.slot = h.d_slot; a.node_id = h.d_id; a.off = h.d_off;
-    const unsigned grid = (unsigned)((K + 3) / 4);
-    hipLaunchKernelGGL(mipx::spill_count, dim3(grid), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(mipx::spill_scan, dim3(1), dim3(1024), 0, st, a);
+    a.slot = h.d_slot; a.node_id = h.d_id; a.off = h.d_off;
+    enqueue_spill_count(a, (int)K, st);
+    enqueue_spill_scan(a, (int)K, st);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(off.data(), h.d_off, ((size_t)K + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1938,7 +2009,7 @@ int spill_event(mipx_tree *t, int64_t target) {
     char *seg = nullptr;
     HIP_TRY(ctx, hipHostMalloc((void **)&seg, (size_t)total, hipHostMallocDefault));
     a.rec = h.d_rec;
-    hipLaunchKernelGGL(mipx::spill_pack, dim3(grid), dim3(256), 0, st, a);
+    enqueue_spill_pack(a, (int)K, st);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(seg, h.d_rec, (size_t)total, hipMemcpyDeviceToHost, st));
     if (hipError_t e = hipStreamSynchronize(st)) {
@@ -2029,8 +2100,8 @@ int spill_reload_enqueue(mipx_tree *t, StepBuf &S) {
     HIP_TRY(ctx, hipMemcpyAsync(S.d_rl + o_rows, S.h_rl + o_rows, (size_t)r * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(S.d_rl + o_rec, S.h_rl + o_rec, (size_t)bytes, hipMemcpyHostToDevice, st));
     mipx::SpillArgs a = spill_args(t);
-    a.count = r; a.off = (int64_t *)S.d_rl; a.slot = (const int32_t *)(S.d_rl + o_rows); a.rec = S.d_rl + o_rec;
-    hipLaunchKernelGGL(mipx::spill_unpack, dim3((unsigned)((r + 3) / 4)), dim3(256), 0, st, a);
+    a.off = (int64_t *)S.d_rl; a.slot = (const int32_t *)(S.d_rl + o_rows); a.rec = S.d_rl + o_rec;
+    enqueue_spill_unpack(a, r, st);
     HIP_TRY(ctx, hipGetLastError());
     return MIPX_OK;
 }
@@ -2492,7 +2563,7 @@ int launch_children(mipx_tree *t, StepBuf &S, hipStream_t cs, int count, const s
         HIP_TRY(ctx, hipMemcpyAsync(d.child_slot, child.data(), 2 * c4, hipMemcpyHostToDevice, cs));
     }
     mipx::ChildArgs ca;
-    ca.n = t->n; ca.m = t->m; ca.count = count;
+    ca.n = t->n; ca.m = t->m;
     ca.src_l = t->pool_l; ca.src_u = t->pool_u; ca.x = S.d_x; ca.vstat = S.d_vout;
     ca.parent_slot = d.parent_slot; ca.parent_pos = d.parent_pos; ca.var = d.var; ca.child_slot = d.child_slot;
     ca.dst_l = dst.l; ca.dst_u = dst.u; ca.dst_v = dst.v;
@@ -2500,7 +2571,7 @@ int launch_children(mipx_tree *t, StepBuf &S, hipStream_t cs, int count, const s
         ca.mstride = t->mrows; ca.kc = t->kc;
         ca.src_ncut = S.w_ncut; ca.src_ids = S.w_ids; ca.dst_ncut = dst.ncut; ca.dst_ids = dst.ids;
     }
-    hipLaunchKernelGGL(mipx::make_children, dim3(2 * count), dim3(256), 0, cs, ca);
+    enqueue_make_children(ca, count, cs);
     HIP_TRY(ctx, hipGetLastError());
     return MIPX_OK;
 }
@@ -3087,8 +3158,7 @@ int mig_pack(mipx_tree *t, const MigLayout &L, char *msg, int32_t *d_slots, int6
     meta[0] = (double)cnt;
     if (cnt > 0) {
         HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, t->st2));
-        pa.count = (int)cnt;
-        hipLaunchKernelGGL(mipx::pack_nodes, dim3((unsigned)cnt), dim3(256), 0, t->st2, pa);
+        enqueue_pack_nodes(pa, (int)cnt, t->st2);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipMemcpyAsync(msg + L.meta_off, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, t->st2));
@@ -3127,8 +3197,7 @@ int mig_unpack(mipx_tree *t, const MigLayout &L, char *msg, int32_t *d_slots, in
     }
     if (cnt > 0) {
         HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, t->st2));
-        pa.count = (int)cnt;
-        hipLaunchKernelGGL(mipx::unpack_nodes, dim3((unsigned)cnt), dim3(256), 0, t->st2, pa);
+        enqueue_unpack_nodes(pa, (int)cnt, t->st2);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipStreamSynchronize(t->st2));
     }
@@ -3174,9 +3243,9 @@ int mig_pack_cuts(mipx_tree *t, const MigLayout &L, char *msg, int32_t *scratch,
         for (int64_t id : cand) slots.push_back(t->nodes[id].slot);
         HIP_TRY(ctx, hipMemcpyAsync(scratch, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, t->st2));
         mipx::CutMigArgs ca;
-        ca.kc = K; ca.count = (int)cand.size(); ca.slot = scratch; ca.pool_ncut = t->pool_ncut; ca.pool_ids = t->pool_ids;
+        ca.kc = K; ca.slot = scratch; ca.pool_ncut = t->pool_ncut; ca.pool_ids = t->pool_ids;
         ca.lists = d_lists;
-        hipLaunchKernelGGL(mipx::cutmig_lists, dim3((unsigned)((cand.size() + 3) / 4)), dim3(256), 0, t->st2, ca);
+        enqueue_cutmig_lists(ca, (int)cand.size(), t->st2);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(lists.data(), d_lists, lists.size() * 4, hipMemcpyDeviceToHost, t->st2));
         HIP_TRY(ctx, hipStreamSynchronize(t->st2));
@@ -3221,8 +3290,7 @@ int mig_pack_cuts(mipx_tree *t, const MigLayout &L, char *msg, int32_t *scratch,
     if (cnt > 0) {
         mipx::PackArgs pa = mig_args(t, L, msg, scratch);
         HIP_TRY(ctx, hipMemcpyAsync(scratch, slots.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, t->st2));
-        pa.count = (int)cnt;
-        hipLaunchKernelGGL(mipx::pack_nodes, dim3((unsigned)cnt), dim3(256), 0, t->st2, pa);
+        enqueue_pack_nodes(pa, (int)cnt, t->st2);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(d_lists, refs.data(), refs.size() * 4, hipMemcpyHostToDevice, t->st2));
     }
@@ -3230,9 +3298,9 @@ int mig_pack_cuts(mipx_tree *t, const MigLayout &L, char *msg, int32_t *scratch,
         int32_t *d_src = mig_src(scratch, amount);
         HIP_TRY(ctx, hipMemcpyAsync(d_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, t->st2));
         mipx::CutMigArgs ca;
-        ca.n = t->n; ca.count = (int)src.size(); ca.src = d_src; ca.store_pi = t->store_pi; ca.store_pi0 = t->store_pi0;
+        ca.n = t->n; ca.src = d_src; ca.store_pi = t->store_pi; ca.store_pi0 = t->store_pi0;
         ca.tab_pi = (double *)(msg + L.tab_off); ca.tab_pi0 = ca.tab_pi + (size_t)L.ctab * t->n;
-        hipLaunchKernelGGL(mipx::cutmig_gather, dim3((unsigned)((src.size() + 3) / 4)), dim3(256), 0, t->st2, ca);
+        enqueue_cutmig_gather(ca, (int)src.size(), t->st2);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipMemcpyAsync(msg + L.meta_off, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, t->st2));
@@ -3283,20 +3351,17 @@ int mig_unpack_cuts(mipx_tree *t, const MigLayout &L, char *msg, int32_t *scratc
         HIP_TRY(ctx, hipMemcpyAsync(scratch, slots.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, t->st2));
         HIP_TRY(ctx, hipMemsetAsync(d_bad, 0, 4, t->st2));
         mipx::PackArgs pa = mig_args(t, L, msg, scratch);
-        pa.count = (int)cnt;
-        hipLaunchKernelGGL(mipx::unpack_nodes, dim3((unsigned)cnt), dim3(256), 0, t->st2, pa);
+        enqueue_unpack_nodes(pa, (int)cnt, t->st2);
         HIP_TRY(ctx, hipGetLastError());
         mipx::CutMigArgs ca;
         ca.n = t->n; ca.kc = L.kc; ca.slot = scratch; ca.pool_ncut = t->pool_ncut; ca.pool_ids = t->pool_ids;
         ca.lists = (int32_t *)(msg + L.refs_off); ca.store_pi = t->store_pi; ca.store_pi0 = t->store_pi0;
         ca.tab_pi = (double *)(msg + L.tab_off); ca.tab_pi0 = ca.tab_pi + (size_t)L.ctab * t->n;
         ca.base = base; ca.ctab = (int)rows; ca.bad = d_bad;
-        ca.count = (int)cnt;
-        hipLaunchKernelGGL(mipx::cutmig_unpack_lists, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, t->st2, ca);
+        enqueue_cutmig_unpack_lists(ca, (int)cnt, t->st2);
         HIP_TRY(ctx, hipGetLastError());
         if (rows > 0) {
-            ca.count = (int)rows;
-            hipLaunchKernelGGL(mipx::cutmig_scatter, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, t->st2, ca);
+            enqueue_cutmig_scatter(ca, (int)rows, t->st2);
             HIP_TRY(ctx, hipGetLastError());
         }
         HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, t->st2));
@@ -4174,14 +4239,13 @@ int mipx_tree_reanchor(mipx_tree *t, int64_t max_nodes) {
         mipx::SpillArgs a = spill_args(t);
         a.kc = 0;   // (the K are plain nodes or no cut rounds run: only bounds and basis codes are needed)
         a.l = sc_l; a.u = sc_u; a.v = sc_v; a.ncut = nullptr; a.ids = nullptr;
-        a.count = (int)K; a.slot = d_sl;
-        hipLaunchKernelGGL(mipx::spill_gather_rows, dim3((unsigned)K), dim3(256), 0, st, a, (const double *)t->pool_l,
-                           (const double *)t->pool_u, (const int8_t *)t->pool_v);
+        a.slot = d_sl;
+        enqueue_spill_gather_rows(a, (int)K, st, t->pool_l, t->pool_u, t->pool_v);
         HIP_TRY(ctx, hipMemcpyAsync(sc_rec, roff.data(), (R + 1) * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(sc_rec + o_pos, pos.data(), R * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(sc_rec + o_rec, recs.data(), recs.size(), hipMemcpyHostToDevice, st));
-        a.count = (int)R; a.off = (int64_t *)sc_rec; a.slot = (const int32_t *)(sc_rec + o_pos); a.rec = sc_rec + o_rec;
-        hipLaunchKernelGGL(mipx::spill_unpack, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a);
+        a.off = (int64_t *)sc_rec; a.slot = (const int32_t *)(sc_rec + o_pos); a.rec = sc_rec + o_rec;
+        enqueue_spill_unpack(a, (int)R, st);
         HIP_TRY(ctx, hipGetLastError());
         idn.resize((size_t)K);
         for (int64_t k = 0; k < K; k++) idn[(size_t)k] = (int32_t)k;
@@ -4198,9 +4262,9 @@ int mipx_tree_reanchor(mipx_tree *t, int64_t max_nodes) {
         HIP_TRY(ctx, hipMalloc((void **)&gu, (size_t)K * n * 8));
         HIP_TRY(ctx, hipMalloc((void **)&gv, (size_t)K * (n + m)));
         mipx::PlainGatherArgs ga;
-        ga.n = (int)n; ga.m = (int)m; ga.nvs_pool = t->n + t->mrows; ga.count = (int)K; ga.slot = d_sl;
+        ga.n = (int)n; ga.m = (int)m; ga.nvs_pool = t->n + t->mrows; ga.slot = d_sl;
         ga.pool_l = src_l; ga.pool_u = src_u; ga.pool_v = src_v; ga.l = gl; ga.u = gu; ga.v = gv;
-        hipLaunchKernelGGL(mipx::gather_plain_nodes, dim3((unsigned)K), dim3(256), 0, st, ga);
+        enqueue_gather_plain_nodes(ga, (int)K, st);
         a.l = gl; a.u = gu; a.vstat_in = gv; a.slot = nullptr;
     }
     if (t->atab_T != nullptr) { a.anchor_sel = d_sl + K; a.atab_T = t->atab_T; a.atab_vec = t->atab_vec; a.atab_idx = t->atab_idx; }
@@ -4640,12 +4704,12 @@ int mipx_tree_cut_rows(mipx_tree *t, int64_t count, const int32_t *ids, double *
     const size_t ids_b = pad8((size_t)count * 4);
     HIP_TRY(ctx, hipMalloc((void **)&blk, ids_b + (size_t)count * (n + 1) * 8));
     mipx::CutMigArgs ca;
-    ca.n = t->n; ca.count = (int)count; ca.src = (const int32_t *)blk; ca.store_pi = t->store_pi; ca.store_pi0 = t->store_pi0;
+    ca.n = t->n; ca.src = (const int32_t *)blk; ca.store_pi = t->store_pi; ca.store_pi0 = t->store_pi0;
     ca.tab_pi = (double *)(blk + ids_b); ca.tab_pi0 = ca.tab_pi + (size_t)count * n;
     int rc = MIPX_OK;
     if (hipMemcpy(blk, ids, (size_t)count * 4, hipMemcpyHostToDevice) != hipSuccess) rc = MIPX_EHIP;
     if (!rc) {
-        hipLaunchKernelGGL(mipx::cutmig_gather, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, ca);
+        enqueue_cutmig_gather(ca, (int)count, ctx->stream);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = MIPX_EHIP;
     }
     if (!rc && pi && hipMemcpy(pi, ca.tab_pi, (size_t)count * n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = MIPX_EHIP;
@@ -4675,6 +4739,7 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "treerec_api.hip.h"
 #include "cglp_api.hip.h"
 #include "restart_api.hip.h"
+#include "noderows_api.hip.h"
 #include "heur_api.hip.h"
 #include "prop_api.hip.h"
 #include "rcfix_api.hip.h"

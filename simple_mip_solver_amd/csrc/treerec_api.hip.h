@@ -90,11 +90,11 @@ int tr_launch_bounds(mipx_tree *t, int cnt, const int64_t *ids, int8_t *out_v) {
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(tr.d_ids, ids, (size_t)cnt * 8, hipMemcpyHostToDevice, st));
     mipx::TrBoundsArgs a;
-    a.n = t->n; a.nv = t->n + t->m; a.count = cnt; a.nodes_count = tr.d_count; a.nodes = tr.d_nodes; a.ids = tr.d_ids;
+    a.n = t->n; a.nv = t->n + t->m; a.nodes_count = tr.d_count; a.nodes = tr.d_nodes; a.ids = tr.d_ids;
     a.root_l = tr.d_root; a.root_u = tr.d_root + t->n; a.root_v = tr.have_root ? tr.d_root_v : nullptr;
     a.out_l = tr.d_l; a.out_u = tr.d_u; a.out_v = out_v;
     HIP_TRY(ctx, hipEventRecord(tr.e0, st));
-    hipLaunchKernelGGL(mipx::treerec_bounds, dim3((unsigned)cnt), dim3(mipx::kTrNT), (size_t)t->n, st, a);
+    enqueue_treerec_bounds(a, cnt, st);
     HIP_TRY(ctx, hipGetLastError());
     tr.materialised += cnt;
     return MIPX_OK;

@@ -41,6 +41,9 @@ __device__ __forceinline__ void tr_apply_lineage(const TrNode *nodes, int64_t no
     while (id > 0 && id < nodes_count) {   // (a parent's id is below its child's: the walk ends at 0)
         const TrNode r = nodes[id];
         const int var = r.vd >> 1, right = r.vd & 1;
+        // (the ownership test is what "no barrier, no atomic" rests on; without it the outputs differ only when a store
+        // overtakes the owner's initialisation, so tests/test_node_rows_abi.py reads it here:
+        // test_the_lineage_walk_keeps_its_ownership_rule)
         if (var >= 0 && var < n && (var % kTrNT) == tid) {
             const uint8_t bit = (uint8_t)(1 << right);
             if (!(seen[var] & bit)) {

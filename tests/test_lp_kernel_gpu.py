@@ -113,6 +113,38 @@ def test_s3_root_children_and_probes(gpu_ctx, oracle):
         assert_same(g2, o2, f'grandchildren of {k}')
 
 
+@pytest.mark.parametrize('n,m', [(64, 32), (300, 150)])   # a register tile; the streamed kernel
+def test_device_pointer_entry_returns_the_bits_of_the_host_entry(n, m, gpu_ctx):
+    """mipx_lp_solve_batch_dev on device buffers of the caller against mipx_lp_solve_batch on the same inputs: every
+    output, bit for bit, warm and cold, to the end and under an iteration limit of 5."""
+    ctx = gpu_ctx
+    A, b, c, l, u, _ = random_dense_milp_arrays(n, m, seed=0)
+    p = _ffi.Problem(ctx, A, b, c)
+    root = p.solve_batch(l[None], u[None])
+    L, U, V = _children(A, b, c, l, u, root, 3)
+    B = len(L)
+    assert B == 6
+    shapes = dict(status=((B,), np.int32), obj=((B,), np.float64), x=((B, n), np.float64), y=((B, m), np.float64),
+                  vstat=((B, n + m), np.int8), iters=((B,), np.int32), npivots=((B,), np.int32))
+    d_l, d_u, d_v = ctx.to_device(L), ctx.to_device(U), ctx.to_device(V)
+    d_out = {k: ctx.to_device(np.full(shape, 0x5a, dtype)) for k, (shape, dtype) in shapes.items()}
+    try:
+        for warm in (True, False):
+            for max_iter in (0, 5):
+                host = p.solve_batch(L, U, V if warm else None, max_iter=max_iter)
+                p.solve_batch_dev(B, d_l, d_u, d_v if warm else None, max_iter, *(d_out[k] for k in shapes))
+                ctx.sync()
+                for k, (shape, dtype) in shapes.items():
+                    got = np.zeros(shape, dtype)
+                    ctx.d2h(got, d_out[k])
+                    assert got.tobytes() == np.ascontiguousarray(host[k], dtype).tobytes(), (n, m, warm, max_iter, k)
+                assert max_iter == 0 or np.all(host['iters'] <= 5)
+    finally:
+        for d in [d_l, d_u, d_v] + list(d_out.values()):
+            ctx.free(d)
+        p.close()
+
+
 def test_with_extra_rows_uses_tall_kernel(gpu_ctx, oracle):
     # m > 128 (cut rows appended) dispatches to the tall instantiation
     A, b, c, l, u, _ = random_dense_milp_arrays(200, 150, seed=3)

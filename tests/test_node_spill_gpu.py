@@ -8,6 +8,7 @@ import pytest
 
 from simple_mip_solver_amd import BranchAndBound, MILPInstance, PseudoCostBranchNode, _ffi
 from simple_mip_solver_amd.generators import random_dense_milp_arrays
+from tests.support.node_rows_reference import encode, random_rows
 
 pytestmark = pytest.mark.gpu
 INF = np.inf
@@ -15,52 +16,6 @@ BIG_POOL = 1 << 20
 
 
 # ---------------------------------------------------------------------------------------------- format
-def pad8(b):
-    return b + bytes((-len(b)) % 8)
-
-
-def encode(root_l, root_u, l, u, v, ncut=None, cut_ids=None):
-    """The record layout of include/mipx_spill.h, written out in numpy."""
-    offsets, out = [0], b''
-    rl, ru = root_l.view(np.uint64), root_u.view(np.uint64)
-    for k in range(l.shape[0]):
-        diff = (l[k].view(np.uint64) != rl) | (u[k].view(np.uint64) != ru)
-        cols = np.nonzero(diff)[0].astype(np.int32)
-        nc = int(ncut[k]) if cut_ids is not None else 0
-        rec = np.array([k], np.int64).tobytes() + np.array([cols.size, nc], np.int32).tobytes()
-        rec += pad8(cols.tobytes()) + l[k, cols].tobytes() + u[k, cols].tobytes()
-        nib = (v[k].astype(np.int16) & 0xF).astype(np.uint8)
-        if nib.size % 2:
-            nib = np.append(nib, np.uint8(0))
-        rec += pad8((nib[0::2] | (nib[1::2] << 4)).astype(np.uint8).tobytes())
-        if cut_ids is not None:
-            rec += pad8(cut_ids[k, :nc].astype(np.int32).tobytes())
-        out += rec
-        offsets.append(len(out))
-    return np.array(offsets, np.int64), np.frombuffer(out, np.uint8)
-
-
-def random_rows(rng, count, n, nv):
-    specials = np.array([INF, -INF, 0.0, -0.0, 1.0, -1.0, 2.5, 1e300])
-    root_l = rng.choice(specials, n)
-    root_u = rng.choice(specials, n)
-    l = np.tile(root_l, (count, 1))
-    u = np.tile(root_u, (count, 1))
-    for k in range(count):
-        if k % 4 == 0:
-            continue                       # no diff at all
-        nd = n if k % 4 == 1 else int(rng.integers(1, n + 1))
-        cols = rng.choice(n, nd, replace=False)
-        l[k, cols] = rng.choice(np.concatenate([specials, rng.normal(size=4)]), nd)
-        u[k, cols[: nd // 2]] = rng.choice(specials, nd // 2)
-        if k % 4 == 2:                     # the sign of a zero alone is a difference
-            z = np.flatnonzero(root_l == 0.0)
-            l[k, z] = -root_l[z] if z.size else l[k, z]
-    v = rng.integers(0, 6, (count, nv)).astype(np.int8)
-    v.flat[:6] = np.arange(6)   # every code at least once
-    return root_l, root_u, l, u, v
-
-
 def same_bits(a, b):
     a, b = np.asarray(a), np.asarray(b)
     if a.dtype == np.float64:
@@ -68,7 +23,10 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a, b)
 
 
-@pytest.mark.parametrize('n,nv,count', [(1, 2, 5), (7, 12, 33), (64, 65, 9), (130, 195, 70), (256, 384, 17)])
+# counts past 1024: spill_scan gives a thread more than one record; n past 256: more than four trips of a wave
+@pytest.mark.parametrize('n,nv,count', [(1, 2, 5), (7, 12, 33), (64, 65, 9), (130, 195, 70), (256, 384, 17), (63, 64, 3),
+                                        (65, 67, 4), (129, 200, 1), (1024, 2047, 5), (3, 5, 1023), (3, 5, 1024), (3, 5, 1025),
+                                        (2, 4, 2049), (5, 9, 4100)])
 def test_pack_is_the_documented_format_and_unpack_inverts_it(n, nv, count, gpu_ctx):
     rng = np.random.default_rng(n * 1000 + nv)
     root_l, root_u, l, u, v = random_rows(rng, count, n, nv)
@@ -80,24 +38,32 @@ def test_pack_is_the_documented_format_and_unpack_inverts_it(n, nv, count, gpu_c
     assert same_bits(l2, l) and same_bits(u2, u) and same_bits(v2, v)
 
 
-@pytest.mark.parametrize('kcut', [1, 5, 64])
-def test_pack_and_unpack_in_cut_mode(kcut, gpu_ctx):
+def cut_mode_round_trip(ctx, kcut, n, count):
     rng = np.random.default_rng(kcut)
-    n, count = 40, 25
     nv = n + 20 + kcut
     root_l, root_u, l, u, v = random_rows(rng, count, n, nv)
     ncut = rng.integers(0, kcut + 1, count).astype(np.int32)
-    ncut[0], ncut[1] = 0, kcut
+    ncut[0], ncut[min(1, count - 1)] = 0, kcut
     ids = rng.integers(0, 1 << 20, (count, kcut)).astype(np.int32)
-    off, recs = _ffi.node_pack_batch(gpu_ctx, root_l, root_u, l, u, v, ncut, ids)
+    off, recs = _ffi.node_pack_batch(ctx, root_l, root_u, l, u, v, ncut, ids)
     ref_off, ref = encode(root_l, root_u, l, u, v, ncut, ids)
     assert same_bits(off, ref_off) and recs.tobytes() == ref.tobytes()
     seed = np.full((count, kcut), -7, np.int32)
-    l2, u2, v2, nc2, ids2 = _ffi.node_unpack_batch(gpu_ctx, root_l, root_u, off, recs, nv, kcut=kcut, cut_ids=seed)
+    l2, u2, v2, nc2, ids2 = _ffi.node_unpack_batch(ctx, root_l, root_u, off, recs, nv, kcut=kcut, cut_ids=seed)
     assert same_bits(l2, l) and same_bits(u2, u) and same_bits(v2, v) and same_bits(nc2, ncut)
     for k in range(count):   # the record's ids; beyond ncut what the caller's buffer held
         assert same_bits(ids2[k, :ncut[k]], ids[k, :ncut[k]])
         assert np.all(ids2[k, ncut[k]:] == -7)
+
+
+@pytest.mark.parametrize('kcut', [1, 5, 64])
+def test_pack_and_unpack_in_cut_mode(kcut, gpu_ctx):
+    cut_mode_round_trip(gpu_ctx, kcut, 40, 25)
+
+
+@pytest.mark.parametrize('kcut,n,count', [(63, 65, 5), (64, 129, 3), (2, 3, 1025), (3, 2, 4100)])
+def test_pack_and_unpack_in_cut_mode_at_other_widths_and_counts(kcut, n, count, gpu_ctx):
+    cut_mode_round_trip(gpu_ctx, kcut, n, count)
 
 
 def test_pack_reports_the_room_it_needs(gpu_ctx):
@@ -211,6 +177,10 @@ def test_spill_run_is_the_big_pool_run(rule, search, batch, dive, cuts, traced, 
         assert spl['st']['status'] == 1 and not spl['st']['pool_exhausted']
         s = spl['spill']
         assert s['spilled'] > 0 and s['reloaded'] > 0 and s['events'] > 0 and s['peak_host_bytes'] > 0
+        # the records one spill event moved: at least the mean, at most the pool's rows and the run's total
+        print(f'spill events [{rule}, {search}, batch {batch}, dive {dive}, cuts {cuts}, traced {trace}]: pool {pool}, '
+              f'{s["spilled"]} records in {s["events"]} events, largest event between {-(-s["spilled"] // s["events"])} and '
+              f'{min(s["spilled"], pool)}')
         assert 0 <= s['on_host'] <= s['spilled'] - s['reloaded']   # (the rest closed unevaluated: dropped)
         assert big['spill']['spilled'] == 0
         if trace:
