@@ -609,6 +609,7 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_finish.h" /* test scaffolding: the device finish of a frontier step on a caller's data */
 #include "mipx_cutround.h" /* test scaffolding: the kernels of a cut round on a caller's data */
 #include "mipx_cglp_screen.h" /* support sessions that keep their duals: dual screen of the leaves, cold retry */
+#include "mipx_supportkernels.h" /* test scaffolding: the kernels behind a support evaluation on a caller's leaves */
 #include "mipx_mir.h"     /* mixed-integer rounding cuts: batched separation of base rows on the GPU */
 #include "mipx_cover.h"   /* lifted knapsack cover cuts: batched separation from the rows on the GPU */
 #include "mipx_dualfn_batch.h" /* test scaffolding: the kernels of the dual function on a caller's records */

@@ -472,6 +472,16 @@ _NODEROWS_SIGNATURES = {
     'mipx_noderows_spill_gather_rows': (_i, [_vp, _i, _i, _i, _vp, _i] + [_vp] * 6),
 }
 NODEROWS_SYMBOLS = list(_NODEROWS_SIGNATURES)
+# ... and those of include/mipx_supportkernels.h (test scaffolding: the kernels behind a support evaluation on a caller's
+# leaves), which mipx.h includes (tests/test_support_kernels_abi.py checks them against that header)
+_SUPPORTKERNELS_SIGNATURES = {
+    'mipx_support_select_batch': (_i, [_vp, _i64, _i, _i, _d, _d] + [_vp] * 12),
+    'mipx_support_pack_batch': (_i, [_vp, _i64, _i, _d] + [_vp] * 8),
+    'mipx_support_gather_batch': (_i, [_vp, _i64, _i64, _i, _i] + [_vp] * 7),
+    'mipx_support_scatter_batch': (_i, [_vp, _i64, _i64, _i, _i, _vp, _i] + [_vp] * 15),
+    'mipx_support_mark_batch': (_i, [_vp, _i64, _vp, _vp]),
+}
+SUPPORTKERNELS_SYMBOLS = list(_SUPPORTKERNELS_SIGNATURES)
 MIR_STATUS = {0: 'cut', 1: 'no_trial', 2: 'shallow', 3: 'dynamism', 4: 'skipped'}   # MIPX_MIR_* of the header
 COVER_STATUS = {0: 'cut', 1: 'no_cover', 2: 'shallow', 4: 'skipped'}   # MIPX_COVER_* of include/mipx_cover.h
 # the defaults of the separation: divisor candidates per row (at most MIR_MAX_DIVISORS), the window of f0, the largest
@@ -508,7 +518,7 @@ def lib():
                                       list(_LPDIVE_SIGNATURES.items()) + list(_FINISH_SIGNATURES.items()) +
                                       list(_CUTROUND_SIGNATURES.items()) + list(_CGLP_SCREEN_SIGNATURES.items()) +
                                       list(_MIR_SIGNATURES.items()) + list(_DUALFN_BATCH_SIGNATURES.items()) +
-                                      list(_NODEROWS_SIGNATURES.items()) +
+                                      list(_NODEROWS_SIGNATURES.items()) + list(_SUPPORTKERNELS_SIGNATURES.items()) +
                                       list(_COVER_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
@@ -1142,6 +1152,57 @@ def noderows_spill_gather_rows(ctx, n, nv, slot, src_l, src_u, src_v, l, u, v):
     rc = lib().mipx_noderows_spill_gather_rows(ctx._h, n, nv, len(slot), _ptr(slot), len(src_l), _ptr(src_l), _ptr(src_u),
                                                _ptr(src_v), _io(l, np.float64), _io(u, np.float64), _io(v, np.int8))
     ctx.check(rc, 'mipx_noderows_spill_gather_rows')
+
+
+# ---- test scaffolding of include/mipx_supportkernels.h: the kernels behind a support evaluation, on a caller's leaves ----
+# The sizes are the caller's (T and count are handed on as given); the in-and-out arrays are written in place, as above.
+def support_select_batch(ctx, T, n, P, pi0, tol, ids, status, obj, x, iters, npivots, margin, cand_m, cand_id, cand_t,
+                         seg_sum, block):
+    """support_select and support_select_merge (mipx_support_select_batch): margin .. block are written in place."""
+    ids, status, obj, x = _arr(ids, np.int64), _arr(status, np.int32), _arr(obj, np.float64), _arr(x, np.float64)
+    iters, npivots = _arr(iters, np.int32), _arr(npivots, np.int32)
+    rc = lib().mipx_support_select_batch(ctx._h, T, n, P, float(pi0), float(tol), _ptr(ids), _ptr(status), _ptr(obj), _ptr(x),
+                                         _ptr(iters), _ptr(npivots), _io(margin, np.float64), _io(cand_m, np.float64),
+                                         _io(cand_id, np.int32), _io(cand_t, np.int32), _io(seg_sum, np.float64),
+                                         _io(block, np.float64))
+    ctx.check(rc, 'mipx_support_select_batch')
+
+
+def support_pack_batch(ctx, T, mode, pi0, skip, status, bound, seg_count, seg_min, packed, info_count, info_min):
+    """support_pack_count and support_pack (mipx_support_pack_batch): seg_count, seg_min, packed and the two one-entry
+    arrays info_count (int32) and info_min (float64) are written in place."""
+    skip, status, bound = _arr(skip, np.uint8), _arr(status, np.int32), _arr(bound, np.float64)
+    rc = lib().mipx_support_pack_batch(ctx._h, T, mode, float(pi0), _ptr(skip), _ptr(status), _ptr(bound), _io(seg_count, np.int32),
+                                       _io(seg_min, np.float64), _io(packed, np.int32), _io(info_count, np.int32),
+                                       _io(info_min, np.float64))
+    ctx.check(rc, 'mipx_support_pack_batch')
+
+
+def support_gather_batch(ctx, count, T, n, m, packed, l, u, v, pl, pu, pv_in):
+    """support_gather (mipx_support_gather_batch): pl, pu, pv_in are written in place; v = None is the cold gather."""
+    packed, l, u, v = _arr(packed, np.int32), _arr(l, np.float64), _arr(u, np.float64), _arr(v, np.int8)
+    rc = lib().mipx_support_gather_batch(ctx._h, count, T, n, m, _ptr(packed), _ptr(l), _ptr(u), _ptr(v), _io(pl, np.float64),
+                                         _io(pu, np.float64), _io(pv_in, np.int8))
+    ctx.check(rc, 'mipx_support_gather_batch')
+
+
+def support_scatter_batch(ctx, count, T, n, m, packed, add, px, pobj, py, pv_out, pstatus, piters, pnpivots, x, obj, y, v,
+                          status, iters, npivots, has_y):
+    """support_scatter (mipx_support_scatter_batch): x .. has_y are written in place."""
+    packed, px, pobj, py = _arr(packed, np.int32), _arr(px, np.float64), _arr(pobj, np.float64), _arr(py, np.float64)
+    pv_out, pstatus, piters, pnpivots = _arr(pv_out, np.int8), _arr(pstatus, np.int32), _arr(piters, np.int32), _arr(pnpivots, np.int32)
+    rc = lib().mipx_support_scatter_batch(ctx._h, count, T, n, m, _ptr(packed), int(add), _ptr(px), _ptr(pobj), _ptr(py),
+                                          _ptr(pv_out), _ptr(pstatus), _ptr(piters), _ptr(pnpivots), _io(x, np.float64),
+                                          _io(obj, np.float64), _io(y, np.float64), _io(v, np.int8), _io(status, np.int32),
+                                          _io(iters, np.int32), _io(npivots, np.int32), _io(has_y, np.uint8))
+    ctx.check(rc, 'mipx_support_scatter_batch')
+
+
+def support_mark_batch(ctx, T, status, has_y):
+    """support_mark (mipx_support_mark_batch): has_y is written in place."""
+    status = _arr(status, np.int32)
+    rc = lib().mipx_support_mark_batch(ctx._h, T, _ptr(status), _io(has_y, np.uint8))
+    ctx.check(rc, 'mipx_support_mark_batch')
 
 
 def solve_multi(ctx, A, b, c, l, u, max_iter=0):

@@ -55,8 +55,6 @@ void sup_free(mipx_support *s) {
     delete s;
 }
 
-int sup_segments(int64_t T) { return (int)((T + mipx::kSupSeg - 1) / mipx::kSupSeg); }
-
 // the ids go up; bounds (and the root's basis codes into d_v[cur]) of all of them, kTrChunk nodes per launch
 int sup_bounds(mipx_support *s) {
     mipx_tree *t = s->t;
@@ -113,7 +111,6 @@ void sup_tick(mipx_support *s, int i, uint32_t &used) {
 
 mipx::SupPackArgs sup_pack_args(mipx_support *s, bool by_status, double pi0) {
     mipx::SupPackArgs a;
-    a.T = (int)s->T; a.G = sup_segments(s->T);
     if (by_status) a.status = s->d_status;
     else { a.skip = s->d_scr; a.bound = s->d_bound; }
     a.pi0 = pi0;
@@ -125,9 +122,9 @@ mipx::SupPackArgs sup_pack_args(mipx_support *s, bool by_status, double pi0) {
 int sup_pack(mipx_support *s, const mipx::SupPackArgs &a, mipx::SupPackInfo *info) {
     mipx_ctx *ctx = s->t->ctx;
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(mipx::support_pack_count, dim3((unsigned)a.G), dim3(mipx::kScrNT), 0, st, a);
+    enqueue_support_pack_count(a, (int)s->T, st);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(mipx::support_pack, dim3((unsigned)a.G), dim3(mipx::kScrNT), 0, st, a);
+    enqueue_support_pack(a, (int)s->T, st);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(info, s->d_info, sizeof *info, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -142,7 +139,7 @@ int sup_solve_packed(mipx_support *s, int count, bool warm, bool add, int pair, 
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)s->n, m = (size_t)s->m, nv = n + m;
     mipx::SupMoveArgs g;
-    g.count = count; g.T = (int)s->T; g.n = s->n; g.m = s->m; g.packed = s->d_pack;
+    g.T = (int)s->T; g.n = s->n; g.m = s->m; g.packed = s->d_pack;
     g.l = s->d_l; g.u = s->d_u; g.x = s->d_x; g.obj = s->d_obj; g.y = s->d_y; g.v = s->d_v[s->cur];
     g.status = s->d_status; g.iters = s->d_iters; g.npivots = s->d_np; g.has_y = s->d_has_y;
     g.pl = s->p_l; g.pu = s->p_u; g.px = s->p_x; g.pobj = s->p_obj; g.py = s->p_y; g.pv_in = s->p_v[0]; g.pv_out = s->p_v[1];
@@ -151,7 +148,7 @@ int sup_solve_packed(mipx_support *s, int count, bool warm, bool add, int pair, 
     mipx::SupMoveArgs in = g;
     if (!warm) in.v = nullptr;
     sup_tick(s, 2 * pair, used);
-    hipLaunchKernelGGL(mipx::support_gather, dim3((unsigned)count), dim3(mipx::kScrNT), 0, st, in);
+    enqueue_support_gather(in, count, st);
     HIP_TRY(ctx, hipGetLastError());
     sup_tick(s, 2 * pair + 1, used);
     for (int64_t k0 = 0; k0 < count; k0 += kTrChunk) {
@@ -170,24 +167,23 @@ int sup_solve_packed(mipx_support *s, int count, bool warm, bool add, int pair, 
     }
     s->lps += count;
     sup_tick(s, 2 * pair + 2, used);
-    hipLaunchKernelGGL(mipx::support_scatter, dim3((unsigned)count), dim3(mipx::kScrNT), 0, st, g);
+    enqueue_support_scatter(g, count, st);
     HIP_TRY(ctx, hipGetLastError());
     sup_tick(s, 2 * pair + 3, used);
     return MIPX_OK;
 }
 
-mipx::SupScreenArgs sup_screen_args(const mipx_problem *p, int T, const double *pi, double pi0, double screen_tol,
+mipx::SupScreenArgs sup_screen_args(const mipx_problem *p, const double *pi, double pi0, double screen_tol,
                                     const double *l, const double *u, const double *y, const uint8_t *has_y,
                                     double *bound, uint8_t *screened) {
     mipx::SupScreenArgs a;
-    a.T = T; a.m = p->m; a.n = p->n; a.pi0 = pi0; a.screen_tol = screen_tol;
+    a.m = p->m; a.n = p->n; a.pi0 = pi0; a.screen_tol = screen_tol;
     a.A = p->dA; a.b = p->db; a.pi = pi; a.l = l; a.u = u; a.y = y; a.has_y = has_y; a.bound = bound; a.screened = screened;
     return a;
 }
 
-int sup_launch_screen(mipx_ctx *ctx, const mipx::SupScreenArgs &a) {
-    const unsigned blocks = (unsigned)((a.T + mipx::kScrWaves - 1) / mipx::kScrWaves);
-    hipLaunchKernelGGL(mipx::support_screen, dim3(blocks), dim3(mipx::kScrNT), 0, ctx->stream, a);
+int sup_launch_screen(mipx_ctx *ctx, const mipx::SupScreenArgs &a, int T) {
+    enqueue_support_screen(a, T, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     return MIPX_OK;
 }
@@ -318,12 +314,12 @@ int mipx_tree_support_eval_ex(mipx_support *s, const double *pi, double pi0, dou
     HIP_TRY(ctx, hipEventRecord(s->e0, st));
     if (s->T > 0 && screening && !s->first) {
         // the leaves whose duals on record prove h_t(pi) >= pi0 - screen_tol get no LP; the others are packed and solved
-        mipx::SupScreenArgs sa = sup_screen_args(t->prob, (int)s->T, s->d_pi, pi0, screen_tol, s->d_l, s->d_u, s->d_y,
+        mipx::SupScreenArgs sa = sup_screen_args(t->prob, s->d_pi, pi0, screen_tol, s->d_l, s->d_u, s->d_y,
                                                  s->d_has_y, s->d_bound, s->d_scr);
         sa.obj = s->d_obj; sa.status = s->d_status; sa.iters = s->d_iters; sa.npivots = s->d_np;
         mipx::SupPackInfo info;
         sup_tick(s, 0, used);
-        if ((rc = sup_launch_screen(ctx, sa))) return rc;
+        if ((rc = sup_launch_screen(ctx, sa, (int)s->T))) return rc;
         rc = sup_pack(s, sup_pack_args(s, false, pi0), &info);
         sup_tick(s, 1, used);
         if (rc) return rc;
@@ -350,8 +346,7 @@ int mipx_tree_support_eval_ex(mipx_support *s, const double *pi, double pi0, dou
         }
         n_solved = s->T;
         if (y && s->T > 0) {   // whose duals are on record now
-            hipLaunchKernelGGL(mipx::support_mark, dim3((unsigned)((s->T + mipx::kScrNT - 1) / mipx::kScrNT)), dim3(mipx::kScrNT), 0, st,
-                               (int)s->T, (const int32_t *)s->d_status, s->d_has_y);
+            enqueue_support_mark((int)s->T, s->d_status, s->d_has_y, st);
             HIP_TRY(ctx, hipGetLastError());
         }
     }
@@ -374,14 +369,14 @@ int mipx_tree_support_eval_ex(mipx_support *s, const double *pi, double pi0, dou
     HIP_TRY(ctx, hipEventRecord(s->e1, st));
     if (s->T > 0) {
         mipx::SupSelectArgs a;
-        a.T = (int)s->T; a.n = s->n; a.P = P; a.G = sup_segments(s->T);
+        a.n = s->n; a.P = P;
         a.pi0 = pi0; a.tol = tol;
         a.ids = s->d_ids; a.status = s->d_status; a.obj = s->d_obj; a.x = s->d_x; a.iters = s->d_iters; a.npivots = s->d_np;
         a.margin = s->d_margin; a.cand_m = s->d_cand_m; a.cand_id = s->d_cand_id; a.cand_t = s->d_cand_t;
         a.seg_sum = s->d_seg; a.block = s->d_block;
-        hipLaunchKernelGGL(mipx::support_select, dim3((unsigned)a.G), dim3(mipx::kSupNT), 0, st, a);
+        enqueue_support_select(a, (int)s->T, st);
         HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(mipx::support_select_merge, dim3(1), dim3(mipx::kSupNT), 0, st, a);
+        enqueue_support_select_merge(a, (int)s->T, st);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(s->e2, st));
@@ -437,16 +432,16 @@ int mipx_support_screen_batch(mipx_problem *p, int64_t T, const double *pi, doub
     if (rc == MIPX_OK && hipMemsetAsync(S.at<char>(o_p), 0xff, K * 4, ctx->stream) != hipSuccess)   // (entries past the count read -1)
         rc = fail(ctx, MIPX_EHIP, "mipx_support_screen_batch: memset");
     if (rc == MIPX_OK)
-        rc = sup_launch_screen(ctx, sup_screen_args(p, (int)T, S.at<const double>(o_pi), pi0, screen_tol, S.at<const double>(o_l),
+        rc = sup_launch_screen(ctx, sup_screen_args(p, S.at<const double>(o_pi), pi0, screen_tol, S.at<const double>(o_l),
                                                     S.at<const double>(o_u), S.at<const double>(o_y), S.at<const uint8_t>(o_h),
-                                                    S.at<double>(o_b), S.at<uint8_t>(o_s)));
+                                                    S.at<double>(o_b), S.at<uint8_t>(o_s)), (int)T);
     if (rc == MIPX_OK) {
         mipx::SupPackArgs a;
-        a.T = (int)T; a.G = (int)G; a.skip = S.at<const uint8_t>(o_s); a.bound = S.at<const double>(o_b); a.pi0 = pi0;
+        a.skip = S.at<const uint8_t>(o_s); a.bound = S.at<const double>(o_b); a.pi0 = pi0;
         a.seg_count = S.at<int32_t>(o_sc); a.seg_min = S.at<double>(o_sm); a.packed = S.at<int32_t>(o_p);
         a.info = S.at<mipx::SupPackInfo>(o_i);
-        hipLaunchKernelGGL(mipx::support_pack_count, dim3((unsigned)G), dim3(mipx::kScrNT), 0, ctx->stream, a);
-        hipLaunchKernelGGL(mipx::support_pack, dim3((unsigned)G), dim3(mipx::kScrNT), 0, ctx->stream, a);
+        enqueue_support_pack_count(a, (int)T, ctx->stream);
+        enqueue_support_pack(a, (int)T, ctx->stream);
         if (hipGetLastError() != hipSuccess) rc = fail(ctx, MIPX_EHIP, "mipx_support_screen_batch: launch");
         else if (hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
             rc = fail(ctx, MIPX_EHIP, "mipx_support_screen_batch: copy");

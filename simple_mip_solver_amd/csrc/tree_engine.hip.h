@@ -106,6 +106,45 @@ void enqueue_spill_gather_rows(mipx::SpillArgs a, int count, hipStream_t st, con
     a.count = count;
     hipLaunchKernelGGL(mipx::spill_gather_rows, dim3((unsigned)count), dim3(256), 0, st, a, src_l, src_u, src_v);
 }
+
+// The one launch site of each kernel behind a support evaluation (cglp_kernels.hip.h, cglp_screen_kernels.hip.h):
+// the leaves T (or the packed leaves `count`) and the segments G are set into the args here and nowhere else, and
+// the grid follows from them.  The session (cglp_api.hip.h), mipx_support_screen_batch and the entries of
+// include/mipx_supportkernels.h (supportkernels_api.hip.h) all launch through these.
+inline int sup_segments(int64_t T) { return (int)((T + mipx::kSupSeg - 1) / mipx::kSupSeg); }
+static_assert(mipx::kSupSeg == mipx::kScrSeg, "the selection and the pack kernels share their segments");
+
+void enqueue_support_screen(mipx::SupScreenArgs a, int T, hipStream_t st) {   // one wave64 per leaf
+    a.T = T;
+    hipLaunchKernelGGL(mipx::support_screen, dim3((unsigned)((T + mipx::kScrWaves - 1) / mipx::kScrWaves)), dim3(mipx::kScrNT), 0, st, a);
+}
+void enqueue_support_pack_count(mipx::SupPackArgs a, int T, hipStream_t st) {
+    a.T = T; a.G = sup_segments(T);
+    hipLaunchKernelGGL(mipx::support_pack_count, dim3((unsigned)a.G), dim3(mipx::kScrNT), 0, st, a);
+}
+void enqueue_support_pack(mipx::SupPackArgs a, int T, hipStream_t st) {
+    a.T = T; a.G = sup_segments(T);
+    hipLaunchKernelGGL(mipx::support_pack, dim3((unsigned)a.G), dim3(mipx::kScrNT), 0, st, a);
+}
+void enqueue_support_gather(mipx::SupMoveArgs a, int count, hipStream_t st) {   // one workgroup per packed leaf
+    a.count = count;
+    hipLaunchKernelGGL(mipx::support_gather, dim3((unsigned)count), dim3(mipx::kScrNT), 0, st, a);
+}
+void enqueue_support_scatter(mipx::SupMoveArgs a, int count, hipStream_t st) {
+    a.count = count;
+    hipLaunchKernelGGL(mipx::support_scatter, dim3((unsigned)count), dim3(mipx::kScrNT), 0, st, a);
+}
+void enqueue_support_mark(int T, const int32_t *status, uint8_t *has_y, hipStream_t st) {
+    hipLaunchKernelGGL(mipx::support_mark, dim3((unsigned)((T + mipx::kScrNT - 1) / mipx::kScrNT)), dim3(mipx::kScrNT), 0, st, T, status, has_y);
+}
+void enqueue_support_select(mipx::SupSelectArgs a, int T, hipStream_t st) {
+    a.T = T; a.G = sup_segments(T);
+    hipLaunchKernelGGL(mipx::support_select, dim3((unsigned)a.G), dim3(mipx::kSupNT), 0, st, a);
+}
+void enqueue_support_select_merge(mipx::SupSelectArgs a, int T, hipStream_t st) {   // one workgroup over the segments' candidates
+    a.T = T; a.G = sup_segments(T);
+    hipLaunchKernelGGL(mipx::support_select_merge, dim3(1), dim3(mipx::kSupNT), 0, st, a);
+}
 }  // namespace
 
 struct NodeRec {
@@ -4740,6 +4779,7 @@ int mipx_tree_spill_stats(mipx_tree *t, int64_t out[8]) {
 #include "cglp_api.hip.h"
 #include "restart_api.hip.h"
 #include "noderows_api.hip.h"
+#include "supportkernels_api.hip.h"
 #include "heur_api.hip.h"
 #include "prop_api.hip.h"
 #include "rcfix_api.hip.h"

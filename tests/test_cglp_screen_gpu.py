@@ -1,7 +1,9 @@
 """The dual screen of the support sessions on the GPU (include/mipx_cglp_screen.h): support_screen and the pack kernels
 against the NumPy restatement bit for bit (tests/support/cglp_screen_reference.py), a screening session against HiGHS
 and against a session without the options, the separator with screen and in-out on the 101-leaf tree whose extended
-formulation HiGHS solves, and the cold retry where no leaf fails."""
+formulation HiGHS solves, and that asking for the cold retry changes nothing where no leaf fails.  No session here
+has a leaf LP that fails, so the retry's own path (the packing by verdict, the cold gather, the scatter of a failed LP
+and of a second LP) is NOT covered here: tests/test_support_kernels_gpu.py runs it on synthetic leaves."""
 import numpy as np
 import pytest
 
