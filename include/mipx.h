@@ -612,6 +612,7 @@ int mipx_kernel_name(int m, int n, char *buf, size_t buflen);
 #include "mipx_supportkernels.h" /* test scaffolding: the kernels behind a support evaluation on a caller's leaves */
 #include "mipx_mir.h"     /* mixed-integer rounding cuts: batched separation of base rows on the GPU */
 #include "mipx_cover.h"   /* lifted knapsack cover cuts: batched separation from the rows on the GPU */
+#include "mipx_clique.h"  /* clique cuts: a conflict graph from the rows, batched greedy separation on the GPU */
 #include "mipx_dualfn_batch.h" /* test scaffolding: the kernels of the dual function on a caller's records */
 #include "mipx_noderows.h"     /* test scaffolding: the kernels that move node rows on a caller's pools */
 

@@ -446,6 +446,13 @@ _COVER_SIGNATURES = {
     'mipx_cover_separate_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _vp, _i, _d] + [_vp] * 5),
 }
 COVER_SYMBOLS = list(_COVER_SIGNATURES)
+# ... and those of include/mipx_clique.h (clique cuts: the conflict graph of the rows and the batched separation), which
+# mipx.h includes (tests/test_clique_abi.py checks them against that header)
+_CLIQUE_SIGNATURES = {
+    'mipx_clique_graph': (_i, [_vp] * 4 + [_i] + [_vp] * 2),
+    'mipx_clique_separate_batch': (_i, [_vp, _i] + [_vp] * 4 + [_i, _vp, _vp, _i, _d] + [_vp] * 5),
+}
+CLIQUE_SYMBOLS = list(_CLIQUE_SIGNATURES)
 # ... and those of include/mipx_dualfn_batch.h (test scaffolding: the kernels of the dual function on a caller's
 # records), which mipx.h includes (tests/test_dualfn_batch_abi.py checks them against that header)
 _DUALFN_BATCH_SIGNATURES = {
@@ -484,6 +491,7 @@ _SUPPORTKERNELS_SIGNATURES = {
 SUPPORTKERNELS_SYMBOLS = list(_SUPPORTKERNELS_SIGNATURES)
 MIR_STATUS = {0: 'cut', 1: 'no_trial', 2: 'shallow', 3: 'dynamism', 4: 'skipped'}   # MIPX_MIR_* of the header
 COVER_STATUS = {0: 'cut', 1: 'no_cover', 2: 'shallow', 4: 'skipped'}   # MIPX_COVER_* of include/mipx_cover.h
+CLIQUE_STATUS = {0: 'cut', 1: 'no_clique', 2: 'shallow', 4: 'skipped'}   # MIPX_CLIQUE_* of include/mipx_clique.h
 # the defaults of the separation: divisor candidates per row (at most MIR_MAX_DIVISORS), the window of f0, the largest
 # ratio of a cut's coefficients
 MIR_MAX_DIVISORS = 64
@@ -519,7 +527,7 @@ def lib():
                                       list(_CUTROUND_SIGNATURES.items()) + list(_CGLP_SCREEN_SIGNATURES.items()) +
                                       list(_MIR_SIGNATURES.items()) + list(_DUALFN_BATCH_SIGNATURES.items()) +
                                       list(_NODEROWS_SIGNATURES.items()) + list(_SUPPORTKERNELS_SIGNATURES.items()) +
-                                      list(_COVER_SIGNATURES.items())):
+                                      list(_COVER_SIGNATURES.items()) + list(_CLIQUE_SIGNATURES.items())):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     _lib = L
@@ -1566,6 +1574,46 @@ class Problem:
         self.ctx.check(rc, 'mipx_cover_separate_batch')
         ms = self.ctx.last_kernel_ms() if B else 0.0
         return dict(pi=pi, pi0=pi0, efficacy=eff, cover_size=size, status=status, kernel_us=max(ms, 0.0) * 1e3)
+
+    def conflict_graph(self, l, u, integer_indices):
+        """The conflict graph of the problem's rows in the box l, u (mipx_clique_graph, include/mipx_clique.h): literal
+        2j is x_j - l_j, literal 2j + 1 its complement.  Returns dict of adj ((2n, Wd) uint32 words, bit k mod 32 of
+        word k div 32 is literal k), row_status (0 used, 4 skipped; m) and kernel_us, the device time of the kernel."""
+        n, m = self.n, self.m
+        l = np.ascontiguousarray(l, dtype=np.float64).reshape(-1)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        assert len(l) == n and len(u) == n, 'l and u hold one box of n columns'
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        adj = np.zeros((2 * n, (2 * n + 31) // 32), np.uint32)
+        row_status = np.zeros(m, np.int32)
+        rc = lib().mipx_clique_graph(self._h, _ptr(l), _ptr(u), _ptr(ii), len(ii), _ptr(adj), _ptr(row_status))
+        self.ctx.check(rc, 'mipx_clique_graph')
+        return dict(adj=adj, row_status=row_status, kernel_us=max(self.ctx.last_kernel_ms(), 0.0) * 1e3)
+
+    def clique_separate_batch(self, X, l, u, integer_indices, adj, seeds=None, min_efficacy=1e-6):
+        """Clique separation on host buffers (mipx_clique_separate_batch, include/mipx_clique.h): X (batch, n) points,
+        l, u one box, adj the (2n, Wd) words of a conflict graph, seeds None (the 2n literals) or R distinct literals
+        shared by the points.  Returns dict of pi (batch, R, n), pi0, efficacy, size, status (CLIQUE_STATUS codes;
+        batch, R each) and kernel_us, the device time of the kernel."""
+        n = self.n
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, n)
+        B = X.shape[0]
+        l = np.ascontiguousarray(l, dtype=np.float64).reshape(-1)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        assert len(l) == n and len(u) == n, 'l and u hold one box of n columns'
+        ii = np.ascontiguousarray(integer_indices, dtype=np.int32).reshape(-1)
+        adj = np.ascontiguousarray(adj, dtype=np.uint32)
+        assert adj.shape == (2 * n, (2 * n + 31) // 32), 'adj holds 2n rows of ceil(2n / 32) words'
+        sd = _arr(seeds, np.int32)
+        R = 2 * n if sd is None else len(sd)
+        pi = np.zeros((B, R, n)); pi0 = np.zeros((B, R)); eff = np.zeros((B, R))
+        size = np.zeros((B, R), np.int32); status = np.zeros((B, R), np.int32)
+        rc = lib().mipx_clique_separate_batch(self._h, B, _ptr(X), _ptr(l), _ptr(u), _ptr(ii), len(ii), _ptr(adj), _ptr(sd),
+                                              0 if sd is None else R, float(min_efficacy), _ptr(pi), _ptr(pi0), _ptr(eff),
+                                              _ptr(size), _ptr(status))
+        self.ctx.check(rc, 'mipx_clique_separate_batch')
+        ms = self.ctx.last_kernel_ms() if B else 0.0
+        return dict(pi=pi, pi0=pi0, efficacy=eff, size=size, status=status, kernel_us=max(ms, 0.0) * 1e3)
 
     def reduced_cost_tighten_batch(self, l, u, y, integer_indices, cutoff, tol=RCFIX_TOL, dtol=RCFIX_DTOL, in_place=False):
         """Reduced-cost bound tightening on host buffers (mipx_reduced_cost_tighten_batch, include/mipx_rcfix.h):

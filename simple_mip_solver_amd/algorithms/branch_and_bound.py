@@ -127,7 +127,7 @@ class BranchAndBound(BaseAlgorithm):
                  host_spill=None, cut_migration=None, dual_function=None, tree_record=None, primal_heuristic=None,
                  propagate=None, reduced_cost=None, objective_step=None, local_search=None, fix_propagate=None,
                  weighted_repair=None, cube_search=None, complete_continuous=None, lp_dive=None, lp_dive_every=None,
-                 root_cuts=None, root_cut_rows=None, cover_cuts=None, **kwargs):
+                 root_cuts=None, root_cut_rows=None, cover_cuts=None, clique_cuts=None, **kwargs):
         """All problems are converted to minimisation with A x >= b on the way in.  **kwargs are
         handed to every bound()/branch() call and refreshed from what those calls return
         (e.g. pseudo_costs={}, strong_branch_iters=5, gomory_cuts=False).
@@ -276,7 +276,14 @@ class BranchAndBound(BaseAlgorithm):
         cover_cuts (extension; needs root_cuts; default None = off): True.  Every round of the root cut loop also
         separates lifted knapsack cover cuts from the model's rows on the GPU (include/mipx_cover.h), one workgroup
         per row, and they compete with the MIR cuts for the round's places.  `root_cuts` then holds both kinds, and
-        `root_cut_stats` counts the MIR cuts selected and kept; counters of the cover cuts: `cover_cut_stats`."""
+        `root_cut_stats` counts the MIR cuts selected and kept; counters of the cover cuts: `cover_cut_stats`.
+        clique_cuts (extension; needs root_cuts; default None = off): True.  Before the first round the conflict graph
+        of the model's rows is built on the GPU (include/mipx_clique.h: two literals x_j - l_j or u_j - x_j of binaries
+        are joined when one row alone keeps them from both being 1), and every round of the root cut loop also grows a
+        clique from each literal at the round's point, one workgroup per literal; the distinct cuts compete with the
+        MIR cuts (and the cover cuts, with cover_cuts) for the round's places.  `root_cuts` then holds all kinds;
+        counters of the clique cuts: `clique_cut_stats`.  On a model without binaries that share rows it finds nothing
+        and changes nothing."""
         assert lp_batch is None or (isinstance(lp_batch, int) and not isinstance(lp_batch, bool) and
                                     lp_batch > 0), 'lp_batch must be a positive integer'
         assert lp_batch is None or frontier_batch is None, \
@@ -448,9 +455,13 @@ class BranchAndBound(BaseAlgorithm):
             'root_cuts cannot be combined with tree_record (and so with restart): a cut depends on the right-hand side'
         assert cover_cuts is None or cover_cuts is True, 'cover_cuts is None or True'
         assert cover_cuts is None or root_cuts is not None, 'cover_cuts needs root_cuts'
+        assert clique_cuts is None or clique_cuts is True, 'clique_cuts is None or True'
+        assert clique_cuts is None or root_cuts is not None, 'clique_cuts needs root_cuts'
         self._root_cuts = 10 if root_cuts is True else root_cuts
         self._cover_cuts = cover_cuts is True
         self.cover_cut_stats = None
+        self._clique_cuts = clique_cuts is True
+        self.clique_cut_stats = None
         self._root_cut_rows = 64 if root_cut_rows is None else root_cut_rows
         self.root_cuts = None
         self.root_cut_stats = None
@@ -582,10 +593,11 @@ class BranchAndBound(BaseAlgorithm):
                 # this point sees an ordinary model (the key names the cut rows, so another row set is another problem)
                 from simple_mip_solver_amd.utils.mir_cuts import root_cut_loop
                 loop = root_cut_loop(rs.A, rs.b, rs.c, l, u, self.model.integerIndices, rounds=self._root_cuts,
-                                     max_rows=self._root_cut_rows, cover=self._cover_cuts)
+                                     max_rows=self._root_cut_rows, cover=self._cover_cuts, clique=self._clique_cuts)
                 self.root_cuts = loop['cuts']
                 self.root_cut_stats = loop['stats']
                 self.cover_cut_stats = loop.get('cover_stats')
+                self.clique_cut_stats = loop.get('clique_stats')
                 problem = backend._problem(loop['A'], loop['b'], rs.c, ('root_cuts', rs.key, loop['A'][rs.A.shape[0]:].tobytes(),
                                                                       loop['b'][rs.A.shape[0]:].tobytes()))
             else:

@@ -12,7 +12,8 @@
 //                   walk.  Lifting counts the mu_h below each item's weight, again by broadcast reads.  The
 //                   coefficients are scattered to a column-indexed LDS array, from which pi, pi0 and the efficacy
 //                   follow in the BLOCK SUM order of mipx_mir.h.  About 40 KiB of LDS.  No atomics; the outputs are
-//                   plain vector stores.
+//                   plain vector stores.  The first stage, the knapsack form up to the compacted items, is the device
+//                   function cover_knapsack_form, which clique_graph (clique_kernels.hip.h) calls too.
 //
 // Products are not fused (the library is built with -ffp-contract=off); every sum runs in the order mipx_cover.h
 // states, which tests/support/cover_reference.py follows bit for bit.
@@ -75,6 +76,77 @@ __device__ inline void cover_prefix_sum(const double *src, int cnt, double (&P)[
     for (int k = 0; k < kCovPer; k++) P[k] = start + P[k];
 }
 
+// KNAPSACK FORM of one row (mipx_cover.h), shared by cover_separate and clique_graph (clique_kernels.hip.h): marks the
+// integer columns in isint, compacts the row's items into wt, col (and key, where the caller has a point: x and key
+// are null together) in column order, and returns their number; W is the capacity, skipped whether the row is skipped.
+// Called by every thread; the arrays are LDS of kCovMax entries each, and the items are published behind the last barrier.
+__device__ inline int cover_knapsack_form(int n, int n_int, const int32_t *int_idx, const double *ar, double bi,
+                                          const double *x, const double *l, const double *u, double *wt, double *key,
+                                          uint16_t *col, uint8_t *isint, double (*red)[kCovNT / 64],
+                                          int (*cnt)[kCovNT / 64], int *sskip, double &W, bool &skipped) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double inf = __builtin_huge_val();
+    for (int j = tid; j < kCovMax; j += kCovNT) isint[j] = 0;
+    if (tid == 0) *sskip = 0;
+    __syncthreads();
+    for (int k = tid; k < n_int; k += kCovNT) isint[int_idx[k]] = 1;
+    __syncthreads();
+
+    // the columns, chunk c of a thread is column tid + 256 c; K; the binaries marked
+    double kpart = 0.0, zero = 0.0;
+    double cw[kCovPer], ck[kCovPer];       // the weight and the key of the item at this thread's chunk c
+    bool cbin[kCovPer], ccomp[kCovPer];   // the column is an item; it is complemented
+#pragma unroll
+    for (int c = 0; c < kCovPer; c++) {
+        const int j = tid + c * kCovNT;
+        cbin[c] = false; ccomp[c] = false; cw[c] = 0.0; ck[c] = 0.0;
+        if (j < n) {
+            const double g = 0.0 - ar[j];
+            if (g != 0.0) {
+                const double lj = l[j], uj = u[j];
+                const bool bin = isint[j] && uj < inf && floor(lj) == lj && floor(uj) == uj && uj - lj == 1.0;
+                const double bnd = g > 0.0 ? lj : uj;
+                if (!bin && !(bnd < inf)) {
+                    *sskip = 1;
+                } else {
+                    kpart += g * bnd;
+                    if (bin) {
+                        cbin[c] = true; ccomp[c] = g < 0.0; cw[c] = fabs(g);
+                        if (x) {
+                            const double xj = x[j];
+                            const double y = g > 0.0 ? xj - lj : uj - xj;
+                            const double yc = y < 0.0 ? 0.0 : y > 1.0 ? 1.0 : y;
+                            ck[c] = (1.0 - yc) / cw[c];   // (the key of the greedy order)
+                        }
+                    }
+                }
+            }
+        }
+        const unsigned long long mask = __ballot(cbin[c]);
+        if (lane == 0) cnt[c][wave] = __popcll(mask);
+    }
+    mir_block_sum2(kpart, zero, red);   // (its barriers also publish cnt and sskip)
+    W = (0.0 - bi) - kpart;
+    skipped = *sskip != 0 || !(W >= 0.0);
+    // the items in column order
+    int nb = 0;
+#pragma unroll
+    for (int c = 0; c < kCovPer; c++) {
+        const unsigned long long mask = __ballot(cbin[c]);
+        int e = nb;
+        for (int w = 0; w < wave; w++) e += cnt[c][w];
+        e += __popcll(mask & ((1ull << lane) - 1ull));
+        if (cbin[c]) {
+            wt[e] = cw[c];
+            if (key) key[e] = ck[c];
+            col[e] = (uint16_t)((tid + c * kCovNT) | (ccomp[c] ? 0x8000 : 0));
+        }
+        nb += (cnt[c][0] + cnt[c][1]) + (cnt[c][2] + cnt[c][3]);
+    }
+    __syncthreads();
+    return nb;
+}
+
 __global__ void __launch_bounds__(kCovNT) cover_separate(CoverArgs a) {
     __shared__ double wt[kCovMax];      // w_e, item order
     __shared__ double key[kCovMax];     // (1 - y*_e) / w_e, item order; then the weights of C0 in the minimal-cover order
@@ -86,73 +158,21 @@ __global__ void __launch_bounds__(kCovNT) cover_separate(CoverArgs a) {
     __shared__ uint8_t isint[kCovMax], inC[kCovMax];
     __shared__ double red[2][kCovNT / 64];
     __shared__ int cnt[kCovPer][kCovNT / 64], redi[kCovNT / 64], sskip;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int n = a.n;
     const size_t blk = blockIdx.x;
     const int rr = (int)(blk % (size_t)a.R);
     const int row = a.rows ? a.rows[rr] : rr;
     const size_t pt = blk / (size_t)a.R;
     const double *x = a.x + pt * n, *l = a.l + pt * n, *u = a.u + pt * n;
-    const double *ar = a.A + (size_t)row * n;
-    const double inf = __builtin_huge_val();
     double *pi = a.pi + blk * n;
 
-    for (int j = tid; j < kCovMax; j += kCovNT) { isint[j] = 0; inC[j] = 0; pic[j] = 0.0; }
-    if (tid == 0) sskip = 0;
-    __syncthreads();
-    for (int k = tid; k < a.n_int; k += kCovNT) isint[a.int_idx[k]] = 1;
-    __syncthreads();
-
-    // KNAPSACK FORM: the columns, chunk c of a thread is column tid + 256 c; K; the binaries marked
-    double kpart = 0.0, zero = 0.0;
-    double cw[kCovPer], ck[kCovPer];       // the weight and the key of the item at this thread's chunk c
-    bool cbin[kCovPer], ccomp[kCovPer];   // the column is an item; it is complemented
-#pragma unroll
-    for (int c = 0; c < kCovPer; c++) {
-        const int j = tid + c * kCovNT;
-        cbin[c] = false; ccomp[c] = false; cw[c] = 0.0; ck[c] = 0.0;
-        if (j < n) {
-            const double g = 0.0 - ar[j];
-            if (g != 0.0) {
-                const double xj = x[j], lj = l[j], uj = u[j];
-                const bool bin = isint[j] && uj < inf && floor(lj) == lj && floor(uj) == uj && uj - lj == 1.0;
-                const double bnd = g > 0.0 ? lj : uj;
-                if (!bin && !(bnd < inf)) {
-                    sskip = 1;
-                } else {
-                    kpart += g * bnd;
-                    if (bin) {
-                        const double y = g > 0.0 ? xj - lj : uj - xj;
-                        cbin[c] = true; ccomp[c] = g < 0.0; cw[c] = fabs(g);
-                        const double yc = y < 0.0 ? 0.0 : y > 1.0 ? 1.0 : y;
-                        ck[c] = (1.0 - yc) / cw[c];   // (the key of the greedy order)
-                    }
-                }
-            }
-        }
-        const unsigned long long mask = __ballot(cbin[c]);
-        if (lane == 0) cnt[c][wave] = __popcll(mask);
-    }
-    mir_block_sum2(kpart, zero, red);   // (its barriers also publish cnt and sskip)
-    const double W = (0.0 - a.b[row]) - kpart;
-    const bool skipped = sskip != 0 || !(W >= 0.0);
+    for (int j = tid; j < kCovMax; j += kCovNT) { inC[j] = 0; pic[j] = 0.0; }   // (published by the barriers of the form)
+    double W, zero = 0.0;
+    bool skipped;
+    const int nb = cover_knapsack_form(n, a.n_int, a.int_idx, a.A + (size_t)row * n, a.b[row], x, l, u, wt, key, col, isint,
+                                       red, cnt, &sskip, W, skipped);
     const double tau = kCovMargin * fmax(1.0, fabs(W));
-    // the items in column order
-    int nb = 0;
-#pragma unroll
-    for (int c = 0; c < kCovPer; c++) {
-        const unsigned long long mask = __ballot(cbin[c]);
-        int e = nb;
-        for (int w = 0; w < wave; w++) e += cnt[c][w];
-        e += __popcll(mask & ((1ull << lane) - 1ull));
-        if (cbin[c]) {
-            wt[e] = cw[c];
-            key[e] = ck[c];
-            col[e] = (uint16_t)((tid + c * kCovNT) | (ccomp[c] ? 0x8000 : 0));
-        }
-        nb += (cnt[c][0] + cnt[c][1]) + (cnt[c][2] + cnt[c][3]);
-    }
-    __syncthreads();
 
     int status = skipped ? 4 : nb < 2 ? 1 : 0;   // (uniform from here on)
     int c0 = 0, r = 0;

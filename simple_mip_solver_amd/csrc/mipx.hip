@@ -427,6 +427,8 @@ int spill_check_records(mipx_ctx *ctx, const char *who, int n, int nv, int kcut,
 #include "mir_api.hip.h"
 #include "cover_kernels.hip.h"
 #include "cover_api.hip.h"
+#include "clique_kernels.hip.h"
+#include "clique_api.hip.h"
 
 extern "C" {
 

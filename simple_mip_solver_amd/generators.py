@@ -43,3 +43,29 @@ def sparse_knapsack_milp_arrays(num_vars, num_cons, row_nonzeros, seed=0):
     cap = np.floor(0.5 * W.sum(1))
     c = rng.integers(5, 31, n).astype(np.float64)
     return -W, -cap, -c, np.zeros(n), np.ones(n), list(range(n))
+
+
+def conflict_packing_milp_arrays(num_vars, num_edges, num_knapsacks, row_nonzeros, seed=0):
+    """Binary packing with pairwise conflicts: max c'x over x in {0, 1}^n with `num_edges` rows x_i + x_j <= 1 and
+    `num_knapsacks` rows W x <= cap of `row_nonzeros` integer weights in 5..30 on columns drawn without replacement,
+    cap = floor(a quarter of the row's weight), c_j in 5..30; handed over as min -c'x, -W x >= -cap.  The LP relaxation
+    of the pair rows sits at 0.5 and neither rounding a row nor covering it moves it: the family the clique cuts of
+    include/mipx_clique.h are measured on.  RNG: numpy Generator(PCG64(seed)): the pairs (i, j), i < j, in
+    lexicographic order, `num_edges` of them drawn without replacement and taken in ascending order; then one
+    knapsack after the other (its columns, then its weights); then c.
+
+    Return (A, b, c, l, u, integer_indices) already in `min c'x, Ax >= b` form."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n, k = int(num_vars), int(row_nonzeros)
+    pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
+    pick = rng.choice(len(pairs), size=int(num_edges), replace=False)
+    W = np.zeros((int(num_edges) + int(num_knapsacks), n))
+    cap = np.ones(len(W))
+    for r, q in enumerate(np.sort(pick)):
+        W[r, list(pairs[q])] = 1.0
+    for r in range(int(num_edges), len(W)):
+        cols = rng.choice(n, size=k, replace=False)
+        W[r, cols] = rng.integers(5, 31, k)
+        cap[r] = np.floor(0.25 * W[r].sum())
+    c = rng.integers(5, 31, n).astype(np.float64)
+    return -W, -cap, -c, np.zeros(n), np.ones(n), list(range(n))

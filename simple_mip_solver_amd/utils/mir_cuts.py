@@ -1,6 +1,7 @@
 """Mixed-integer rounding cuts (include/mipx_mir.h): stand-alone separation on the GPU for users of lp_batch or of a
 loop of their own, the tableau rows of a basis as base rows, and the root cut loop behind
-BranchAndBound(root_cuts=...), which with cover=True also takes the lifted cover cuts of include/mipx_cover.h."""
+BranchAndBound(root_cuts=...), which with cover=True also takes the lifted cover cuts of include/mipx_cover.h and with
+clique=True the clique cuts of include/mipx_clique.h."""
 from math import cos, radians
 
 import numpy as np
@@ -124,6 +125,15 @@ class GpuRows:
         return dict(pi=r['pi'][0], pi0=r['pi0'][0], efficacy=r['efficacy'][0], status=r['status'][0],
                     kernel_us=r['kernel_us'])
 
+    def conflict_graph(self, l, u, int_idx):
+        r = self.problem.conflict_graph(l, u, int_idx)
+        return dict(adj=r['adj'], row_status=r['row_status'], kernel_us=r['kernel_us'])
+
+    def separate_clique(self, x, l, u, int_idx, adj, min_efficacy):
+        r = self.problem.clique_separate_batch(x[None], l, u, int_idx, adj, None, min_efficacy)
+        return dict(pi=r['pi'][0], pi0=r['pi0'][0], efficacy=r['efficacy'][0], status=r['status'][0],
+                    kernel_us=r['kernel_us'])
+
     def close(self):
         self.problem.close()
 
@@ -158,7 +168,7 @@ def _chosen_places(sep, chosen):
 def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_rows=DEFAULT_ROOT_CUT_ROWS,
                   max_cuts_per_round=16, max_tableau_rows=64, parallel_cut_tolerance=tol.parallel_cut_tolerance,
                   cutting_plane_progress_tolerance=tol.cutting_plane_progress_tolerance, make_rows=GpuRows, cover=False,
-                  cover_min_efficacy=1e-6, **params):
+                  cover_min_efficacy=1e-6, clique=False, clique_min_efficacy=1e-6, **params):
     """Rounds of MIR separation at the root of min c x, A x >= b, l <= x <= u with the integer columns int_idx.
 
     Every round solves the LP over the model's rows and the cut rows alive (warm from the last basis, new rows basic),
@@ -173,9 +183,16 @@ def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_ro
     the cut rows, in a second launch.  Their candidates stand behind the MIR candidates in the selection, so a tie in
     efficacy goes to the MIR row.
 
+    clique=True: the conflict graph of include/mipx_clique.h is built once, from the first row set (the model's rows
+    alone) and the box l, u, and every round also grows a clique from each of the 2n literals at the round's point, in
+    a launch behind the other two.  The status-0 cuts are reduced to the distinct (pi, pi0), the first seed's kept, and
+    stand behind the MIR and the cover candidates in the selection.
+
     Returns dict(cuts=[(pi, pi0)], A, b (the model's rows and the cuts), vstat (the last basis or None), stats), and
-    with cover=True also cover_stats (rounds, rows, found, skipped, selected, kept, kernel_us); `selected` and `kept`
-    of stats then count the MIR cuts alone, so the cuts returned are stats['kept'] + cover_stats['kept']."""
+    with cover=True also cover_stats (rounds, rows, found, skipped, selected, kept, kernel_us), with clique=True also
+    clique_stats (rounds, seeds, found (distinct), selected, kept, edges, rows_skipped, kernel_us (the graph and the
+    separations)); `selected` and `kept` of stats then count the MIR cuts alone, so the cuts returned are
+    stats['kept'] + cover_stats['kept'] + clique_stats['kept']."""
     A, b, c = np.asarray(A, np.float64), np.asarray(b, np.float64), np.asarray(c, np.float64)
     l, u = np.asarray(l, np.float64), np.asarray(u, np.float64)
     m0, n = A.shape
@@ -188,7 +205,9 @@ def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_ro
     stats = dict(rounds=0, base_rows=0, found=0, selected=0, kept=0, bound_before=None, bound_after=None, lp_pivots=0,
                  kernel_us=0.0)
     cover_stats = dict(rounds=0, rows=0, found=0, skipped=0, selected=0, kept=0, kernel_us=0.0) if cover else None
-    from_cover = []   # one flag per cut alive: it came from the cover separation
+    clique_stats = dict(rounds=0, seeds=0, found=0, selected=0, kept=0, edges=0, rows_skipped=0, kernel_us=0.0) if clique else None
+    adj = None        # the packed conflict graph, built before the first clique separation
+    kind = []         # one code per cut alive: 0 a MIR cut, 1 from the cover separation, 2 from the clique separation
 
     def rows_of(cuts):
         if not cuts:
@@ -220,7 +239,7 @@ def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_ro
                             and vstat[n + m0 + k] == 1)]
             if len(keep) < len(cuts):
                 cuts = [cuts[k] for k in keep]
-                from_cover = [from_cover[k] for k in keep]
+                kind = [kind[k] for k in keep]
                 vstat = np.concatenate([vstat[:n + m0], vstat[n + m0:][keep]])
                 Ak, bk = rows_of(cuts)
                 rows = None
@@ -254,27 +273,55 @@ def root_cut_loop(A, b, c, l, u, int_idx, rounds=DEFAULT_ROOT_CUT_ROUNDS, max_ro
             cover_stats['skipped'] += int(np.sum(cov['status'] == 4))
             cover_stats['kernel_us'] += cov.get('kernel_us', 0.0)
             sep = {key: np.concatenate([sep[key], cov[key]]) for key in ('pi', 'pi0', 'efficacy', 'status')}
+        n_cover = len(sep['status'])
+        if clique:
+            if adj is None:
+                g = made[0].conflict_graph(l, u, ints)
+                adj = g['adj']
+                clique_stats['edges'] = int(np.unpackbits(np.ascontiguousarray(adj).view(np.uint8)).sum()) // 2
+                clique_stats['rows_skipped'] = int(np.sum(g['row_status'] == 4))
+                clique_stats['kernel_us'] += g.get('kernel_us', 0.0)
+            clq = rows.separate_clique(x, l, u, ints, adj, clique_min_efficacy)
+            seen, places = set(), []   # the distinct (pi, pi0) of the status-0 seeds, the first seed's kept
+            for k in np.flatnonzero(clq['status'] == 0):
+                cut = (clq['pi'][k].tobytes(), float(clq['pi0'][k]))
+                if cut not in seen:
+                    seen.add(cut)
+                    places.append(k)
+            clique_stats['rounds'] += 1
+            clique_stats['seeds'] += len(clq['status'])
+            clique_stats['found'] += len(places)
+            clique_stats['kernel_us'] += clq.get('kernel_us', 0.0)
+            places = np.asarray(places, dtype=np.int64)
+            sep = {key: np.concatenate([sep[key], clq[key][places]]) for key in ('pi', 'pi0', 'efficacy', 'status')}
         chosen = select_cuts(sep['pi'], sep['pi0'], sep['efficacy'], sep['status'], cuts, room, max_cuts_per_round, cos_par)
         if not chosen:
             break
-        # which of the chosen are cover cuts: select_cuts copies the rows, so they are found again by their place
-        flags = [k >= n_mir for k in _chosen_places(sep, chosen)] if cover else [False] * len(chosen)
-        stats['selected'] += len(chosen) - sum(flags)
+        # which kind each chosen cut is: select_cuts copies the rows, so they are found again by their place
+        codes = [0 if k < n_mir else 1 if k < n_cover else 2 for k in _chosen_places(sep, chosen)] if cover or clique \
+            else [0] * len(chosen)
+        stats['selected'] += codes.count(0)
         if cover:
-            cover_stats['selected'] += sum(flags)
-        from_cover = from_cover + flags
+            cover_stats['selected'] += codes.count(1)
+        if clique:
+            clique_stats['selected'] += codes.count(2)
+        kind = kind + codes
         cuts = cuts + chosen
         vstat = np.concatenate([vstat, np.ones(len(chosen), np.int8)])
     for rows in made:   # (the row sets of the rounds: their device buffers go now)
         if hasattr(rows, 'close'):
             rows.close()
-    stats['kept'] = len(cuts) - sum(from_cover)
+    stats['kept'] = kind.count(0)
     if cover:
-        cover_stats['kept'] = sum(from_cover)
+        cover_stats['kept'] = kind.count(1)
+    if clique:
+        clique_stats['kept'] = kind.count(2)
     Ak, bk = rows_of(cuts)
     if vstat is not None and len(vstat) != n + Ak.shape[0]:
         vstat = None
     out = dict(cuts=cuts, A=np.ascontiguousarray(Ak), b=np.ascontiguousarray(bk), vstat=vstat, stats=stats)
     if cover:
         out['cover_stats'] = cover_stats
+    if clique:
+        out['clique_stats'] = clique_stats
     return out
